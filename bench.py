@@ -7,14 +7,17 @@ Rows shard by range across ranks with no data-path collective (weak scaling: eve
 torch.distributed (nccl = RCCL) is used for the barrier and the max-over-ranks timing — and, in configs[4] only,
 for the one real exchange of the path (hash-partition all-to-all).
 
-    python bench.py [--workload csv|configs0|configs2|configs3|configs4|configs4d|json|sr|sr_proto|collapse|debezium|debezium_sr] --gpus 1 --steps K --warmup W
+    python bench.py [--workload csv|configs0|configs2|configs3|configs4|configs4d|json|sr|sr_proto|collapse|debezium|debezium_sr] --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (DESIGN.md "Measurement" explains every field).  Every workload reports `roofline` (dominant
-kernel: algorithmic bytes per launch ÷ its HIP-event launch time, against the 8 TB/s HBM peak), `cpu_baseline` (the oracle — a C
-restatement of the Go reference — on a bounded sample of the same input) and `parity` (the device's output for that sample against
-the oracle's).  The default line also carries `other_configs`: configs 0 / 2 / 3 / 4 and the Debezium parser, each run as its own
-short bench after the headline's timed region (rows/s, ms per pass, dominant kernel + fraction of the HBM peak, parity).
+Prints ONE JSON line on rank 0 (DESIGN.md "Measurement" explains every field).  A plain run sets up, warms up, times the K steps
+and prints the headline (`value`, `ms_per_step`, ...).  With --full every workload also reports `kernels` (the per-kernel HIP-event
+pass), `roofline` (dominant kernel: algorithmic bytes per launch ÷ its HIP-event launch time, against the 8 TB/s HBM peak),
+`cpu_baseline` (the oracle — a C restatement of the Go reference — on a bounded sample of the same input), `parity` (the device's
+output for that sample against the oracle's) and its side measurements; the default line then also carries `other_configs`:
+configs 0 / 2 / 3 / 4 and the Debezium parser, each run as its own short bench after the headline's timed region (rows/s, ms per
+pass, dominant kernel + fraction of the HBM peak, parity).  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (csv workload: bench/wl_csv.py dump_outputs).
 
 The code lives in bench/ (common.py, cpu_workers.py, pipeline.py, wl_*.py, main.py); this file is the entry point the driver runs.
 """

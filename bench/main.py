@@ -1,5 +1,5 @@
 """bench/main.py — the driver contract of bench.py: argument parsing, the timed region (barrier + device sync on both sides, MAX over ranks),
-the per-kernel HIP-event pass, roofline / cpu_baseline / parity blocks, and ONE JSON line on rank 0."""
+--dump-outputs, under --full the per-kernel HIP-event pass, roofline / cpu_baseline / parity blocks and side measurements, and ONE JSON line on rank 0."""
 from .common import *  # noqa: F401,F403
 from .wl_csv import CsvWorkload
 from .wl_messages import JsonWorkload, SrWorkload
@@ -27,7 +27,7 @@ def other_configs(args):
     out = {}
     for w, which, extra in OTHER_CONFIGS:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--gpus", "1", "--steps", "8", "--warmup", "2", "--pcie-steps", "0",
-               "--cpu-rows", str(1 << 16), "--cpu-all-rows", "0", "--parity-rows", str(args.parity_rows), "--other-configs", "0"] + (extra or ["--overlap-lanes", "0"])
+               "--cpu-rows", str(1 << 16), "--cpu-all-rows", "0", "--parity-rows", str(args.parity_rows), "--other-configs", "0", "--full"] + (extra or ["--overlap-lanes", "0"])
         t0 = time.perf_counter()
         try:
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
@@ -92,7 +92,13 @@ def main():
     ap.add_argument("--other-configs", type=int, default=1, help="csv workload at N=1: 1 = after the headline's own measurements, run configs0 / 2 / 3 / 4 and debezium as short benches of their own and "
                     "carry a digest of each line (rows/s, ms per pass, dominant kernel + fraction of the HBM peak, parity) as `other_configs`; 0 = skip")
     ap.add_argument("--exchange", type=int, default=1, help="configs4 at 1 rank: 1 = every buffer still makes the RCCL round trip, 0 = skip the collective")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: the per-kernel HIP-event pass, roofline, cpu_baseline + parity, "
+                    "the side measurements and (csv) other_configs.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32 / float64, a fixed seeded sample of the larger arrays, at most 64 MB in all; csv workload)")
     args = ap.parse_args()
+    if args.dump_outputs and not hasattr(WORKLOADS[args.workload], "dump_outputs"):
+        raise SystemExit("--dump-outputs is implemented for the csv workload, not for --workload %s" % args.workload)
 
     import torch  # first: libtfgpu and torch must share the HIP runtime torch loads
     from transferia_amd import abi, dist as tdist, lib, workload
@@ -163,6 +169,7 @@ def main():
         lib.synchronize()
         pr.disable()
         pstats.Stats(pr, stream=sys.stderr).sort_stats("tottime").print_stats(18)
+    W.hold_last = bool(args.dump_outputs)
     my_dt = W.timed(args.steps * passes)
     dt = e.group.max_seconds(my_dt)
     W.dt = dt
@@ -171,98 +178,103 @@ def main():
     rank_rows = e.group.all_gather_float(float(W.rows() * passes))
     ranks_seen = e.group.sum_int(1)
     ms_per_pass = dt / (args.steps * passes) * 1e3
+    if args.dump_outputs:  # what the last timed step computed, held by W.timed instead of freed
+        W.dump_outputs(args.dump_outputs if rank == 0 else None)
 
-    # ---- per-kernel device time: HIP events on the library stream, IMMEDIATELY after the timed region (before any side
-    #      measurement touches clocks, lanes or PCIe), 2 warm-up passes, then >= 10 passes read back one by one: the figure kept
-    #      per kernel is the MEDIAN over passes of (sum of its launches in the pass) ----
-    lib.prof_reset(); lib.prof_enable(True)
-    for _ in range(2):
-        W.step()
-    lib.prof_reset()
-    per_pass, units = {}, {}
-    nprof = max(args.prof_steps, 1)
-    for i in range(nprof):
-        W.step()
-        for n, l, ms in lib.prof_get():
-            if l:
-                per_pass.setdefault(n, []).append((l, ms))
-        for n, u in lib.prof_units().items():
-            if u:
-                units.setdefault(n, []).append(u)
+    # ---- everything beyond the headline figure runs under --full only: a plain run is set-up, warm-up, the timed steps and the line
+    kernels, side, roofline, int_roof, cpu = {}, {}, None, None, None
+    if args.full:
+        # ---- per-kernel device time: HIP events on the library stream, IMMEDIATELY after the timed region (before any side
+        #      measurement touches clocks, lanes or PCIe), 2 warm-up passes, then >= 10 passes read back one by one: the figure kept
+        #      per kernel is the MEDIAN over passes of (sum of its launches in the pass) ----
+        lib.prof_reset(); lib.prof_enable(True)
+        for _ in range(2):
+            W.step()
         lib.prof_reset()
-    lib.prof_enable(False)
-    kernels = {}
-    for n, samples in per_pass.items():
-        if len(samples) < nprof:  # not launched in every pass: averaged over all passes
-            ms_step = sum(ms for _, ms in samples) / nprof
-            lps = sum(l for l, _ in samples) / nprof
-        else:
-            ms_step = float(np.median([ms for _, ms in samples]))
-            lps = float(np.median([l for l, _ in samples]))
-        kernels[n] = {"launches_per_step": lps, "avg_ms": ms_step / max(lps, 1e-9), "ms_per_step": ms_step}
-        if units.get(n):  # the rows the kernel's launches were issued over, as the library counted them (tfgpu_prof_get_units)
-            kernels[n]["units_per_step"] = int(np.median(units[n]))
-    kernel_sum_ms = sum(v["ms_per_step"] for v in kernels.values())
+        per_pass, units = {}, {}
+        nprof = max(args.prof_steps, 1)
+        for i in range(nprof):
+            W.step()
+            for n, l, ms in lib.prof_get():
+                if l:
+                    per_pass.setdefault(n, []).append((l, ms))
+            for n, u in lib.prof_units().items():
+                if u:
+                    units.setdefault(n, []).append(u)
+            lib.prof_reset()
+        lib.prof_enable(False)
+        kernels = {}
+        for n, samples in per_pass.items():
+            if len(samples) < nprof:  # not launched in every pass: averaged over all passes
+                ms_step = sum(ms for _, ms in samples) / nprof
+                lps = sum(l for l, _ in samples) / nprof
+            else:
+                ms_step = float(np.median([ms for _, ms in samples]))
+                lps = float(np.median([l for l, _ in samples]))
+            kernels[n] = {"launches_per_step": lps, "avg_ms": ms_step / max(lps, 1e-9), "ms_per_step": ms_step}
+            if units.get(n):  # the rows the kernel's launches were issued over, as the library counted them (tfgpu_prof_get_units)
+                kernels[n]["units_per_step"] = int(np.median(units[n]))
+        kernel_sum_ms = sum(v["ms_per_step"] for v in kernels.values())
 
-    side = W.side_measurements() if hasattr(W, "side_measurements") else {}
-    if "overlapped_lanes" not in side and args.overlap_lanes > 1 and world == 1 and not getattr(e, "devices", None) and args.workload not in ("csv", "configs0", "configs2", "configs3"):
-        ols = [W.overlapped_lanes(args.overlap_lanes, max(min(args.steps * passes, 60), 6)) for _ in range(int(os.environ.get("TFGPU_BENCH_OL_REPEAT", "3")))]   # the message workloads: see Base.overlapped_lanes
-        ols = [o for o in ols if o]
-        if ols:
-            good = sorted((o for o in ols if "rows_per_s" in o), key=lambda o: o["rows_per_s"])
-            ol = dict(good[len(good) // 2]) if good else ols[0]   # the median of the repeats; all of them listed
-            if good:
-                ol["repeats_rows_per_s"] = [o["rows_per_s"] for o in ols if "rows_per_s" in o]
-            side = dict(side); side["overlapped_lanes"] = ol
+        side = W.side_measurements() if hasattr(W, "side_measurements") else {}
+        if "overlapped_lanes" not in side and args.overlap_lanes > 1 and world == 1 and not getattr(e, "devices", None) and args.workload not in ("csv", "configs0", "configs2", "configs3"):
+            ols = [W.overlapped_lanes(args.overlap_lanes, max(min(args.steps * passes, 60), 6)) for _ in range(int(os.environ.get("TFGPU_BENCH_OL_REPEAT", "3")))]   # the message workloads: see Base.overlapped_lanes
+            ols = [o for o in ols if o]
+            if ols:
+                good = sorted((o for o in ols if "rows_per_s" in o), key=lambda o: o["rows_per_s"])
+                ol = dict(good[len(good) // 2]) if good else ols[0]   # the median of the repeats; all of them listed
+                if good:
+                    ol["repeats_rows_per_s"] = [o["rows_per_s"] for o in ols if "rows_per_s" in o]
+                side = dict(side); side["overlapped_lanes"] = ol
 
-    W.kernels = kernels
-    alg = W.alg()
-    dom = max(kernels.items(), key=lambda kv: kv[1]["ms_per_step"])[0] if kernels else None
-    roofline = None
-    if dom and alg.get(dom) and not emu:   # (the emulator's events carry no time)
-        per_launch = alg[dom] / max(kernels[dom]["launches_per_step"], 1)
-        # The kernels of a pass cannot take longer than the pass that contains them.  When the event pass says otherwise (another
-        # clock state, a noisy box) the dominant kernel is bounded from the TIMED region instead: pass time minus the other kernels.
-        consistent = kernel_sum_ms <= 1.05 * ms_per_pass
-        launch_ms, source = kernels[dom]["avg_ms"], "hip_events_median"
-        if not consistent:
-            others = kernel_sum_ms - kernels[dom]["ms_per_step"]
-            bound_ms = max(ms_per_pass - others * ms_per_pass / kernel_sum_ms, 1e-6) if others >= ms_per_pass else ms_per_pass - others
-            launch_ms, source = bound_ms / max(kernels[dom]["launches_per_step"], 1), "upper bound: timed pass minus the other kernels (event pass inconsistent with the timed region)"
-        achieved = per_launch / (launch_ms * 1e-3) / 1e9
-        # HBM traffic per launch cannot be read inside this process: it comes from the rocprofv3 --pmc passes of tools/gpu_visit.sh
-        # (FETCH_SIZE + WRITE_SIZE with the guide's gfx950 corrections), which stamp profiles/pmc_traffic.json with the sha256 of
-        # the kernel's source file — a number measured on another build of the kernel (or another launch shape) is not printed.
-        traffic = None
-        try:
-            import hashlib
-            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-                t = json.load(f).get(dom)
-            if t and t["rows_per_launch"] == W.rows() and t.get("workload", "csv") == args.workload:
-                with open(os.path.join(ROOT, "transferia_amd", "csrc", t["source_file"]), "rb") as f:
-                    fresh = hashlib.sha256(f.read()).hexdigest() == t["source_sha256"]
-                traffic = t["bytes_per_launch"] if fresh else None
-        except (OSError, ValueError, KeyError):
-            pass
-        roofline = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                    "traffic": traffic, "algorithmic_bytes_per_launch": int(per_launch), "avg_launch_ms": round(launch_ms, 4), "launch_ms_source": source,
-                    "consistent": bool(consistent), "kernels_ms_per_pass": round(kernel_sum_ms, 4), "timed_ms_per_pass": round(ms_per_pass, 4), "event_passes": nprof}
-        # `achieved` counts the conservative figure (input bytes + fixed-width values).  The CSV parse kernel also writes a (length, position)
-        # pair per text cell — the late-materialised form of SURVEY 8(d)'s "every output column byte", 8 bytes per cell instead of offset + text:
-        # stated next to it, never instead of it
-        extra = W.alg_views().get(dom) if hasattr(W, "alg_views") else None
-        if extra:
-            extra = extra / max(kernels[dom]["launches_per_step"], 1)
-            roofline["text_view_bytes_per_launch"] = int(extra)
-            roofline["frac_with_text_views"] = round((per_launch + extra) / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-    int_roof = W.int_roofline(kernels) if not emu else None
-    for k, v in kernels.items():
-        b = alg.get(k)
-        if b and v["avg_ms"] > 0:
-            v["alg_gb_s"] = round(b / max(v["launches_per_step"], 1) / (v["avg_ms"] * 1e-3) / 1e9, 2)
-        v["avg_ms"], v["ms_per_step"] = round(v["avg_ms"], 4), round(v["ms_per_step"], 4)
+        W.kernels = kernels
+        alg = W.alg()
+        dom = max(kernels.items(), key=lambda kv: kv[1]["ms_per_step"])[0] if kernels else None
+        roofline = None
+        if dom and alg.get(dom) and not emu:   # (the emulator's events carry no time)
+            per_launch = alg[dom] / max(kernels[dom]["launches_per_step"], 1)
+            # The kernels of a pass cannot take longer than the pass that contains them.  When the event pass says otherwise (another
+            # clock state, a noisy box) the dominant kernel is bounded from the TIMED region instead: pass time minus the other kernels.
+            consistent = kernel_sum_ms <= 1.05 * ms_per_pass
+            launch_ms, source = kernels[dom]["avg_ms"], "hip_events_median"
+            if not consistent:
+                others = kernel_sum_ms - kernels[dom]["ms_per_step"]
+                bound_ms = max(ms_per_pass - others * ms_per_pass / kernel_sum_ms, 1e-6) if others >= ms_per_pass else ms_per_pass - others
+                launch_ms, source = bound_ms / max(kernels[dom]["launches_per_step"], 1), "upper bound: timed pass minus the other kernels (event pass inconsistent with the timed region)"
+            achieved = per_launch / (launch_ms * 1e-3) / 1e9
+            # HBM traffic per launch cannot be read inside this process: it comes from the rocprofv3 --pmc passes of tools/gpu_visit.sh
+            # (FETCH_SIZE + WRITE_SIZE with the guide's gfx950 corrections), which stamp profiles/pmc_traffic.json with the sha256 of
+            # the kernel's source file — a number measured on another build of the kernel (or another launch shape) is not printed.
+            traffic = None
+            try:
+                import hashlib
+                with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+                    t = json.load(f).get(dom)
+                if t and t["rows_per_launch"] == W.rows() and t.get("workload", "csv") == args.workload:
+                    with open(os.path.join(ROOT, "transferia_amd", "csrc", t["source_file"]), "rb") as f:
+                        fresh = hashlib.sha256(f.read()).hexdigest() == t["source_sha256"]
+                    traffic = t["bytes_per_launch"] if fresh else None
+            except (OSError, ValueError, KeyError):
+                pass
+            roofline = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                        "traffic": traffic, "algorithmic_bytes_per_launch": int(per_launch), "avg_launch_ms": round(launch_ms, 4), "launch_ms_source": source,
+                        "consistent": bool(consistent), "kernels_ms_per_pass": round(kernel_sum_ms, 4), "timed_ms_per_pass": round(ms_per_pass, 4), "event_passes": nprof}
+            # `achieved` counts the conservative figure (input bytes + fixed-width values).  The CSV parse kernel also writes a (length, position)
+            # pair per text cell — the late-materialised form of SURVEY 8(d)'s "every output column byte", 8 bytes per cell instead of offset + text:
+            # stated next to it, never instead of it
+            extra = W.alg_views().get(dom) if hasattr(W, "alg_views") else None
+            if extra:
+                extra = extra / max(kernels[dom]["launches_per_step"], 1)
+                roofline["text_view_bytes_per_launch"] = int(extra)
+                roofline["frac_with_text_views"] = round((per_launch + extra) / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+        int_roof = W.int_roofline(kernels) if not emu else None
+        for k, v in kernels.items():
+            b = alg.get(k)
+            if b and v["avg_ms"] > 0:
+                v["alg_gb_s"] = round(b / max(v["launches_per_step"], 1) / (v["avg_ms"] * 1e-3) / 1e9, 2)
+            v["avg_ms"], v["ms_per_step"] = round(v["avg_ms"], 4), round(v["ms_per_step"], 4)
 
-    cpu = W.cpu() if (rank == 0 and world == 1 and args.cpu_rows > 0) else None  # the oracle, rank 0, N = 1 only
+        cpu = W.cpu() if (rank == 0 and world == 1 and args.cpu_rows > 0) else None  # the oracle, rank 0, N = 1 only
 
     if rank == 0:
         rows = W.rows()
@@ -287,12 +299,13 @@ def main():
         if emu:
             out["emulated"] = "tools/hipemu (CPU): a structural run of this command line, not a measurement"
         out["row_errors"] = W.state.get("errors", 0)
-        out["roofline"] = roofline
-        if int_roof:
-            out["int_roofline"] = int_roof
-        out["cpu_baseline"] = cpu
-        out["kernels"] = kernels
-        out.update(side)
+        if args.full:
+            out["roofline"] = roofline
+            if int_roof:
+                out["int_roofline"] = int_roof
+            out["cpu_baseline"] = cpu
+            out["kernels"] = kernels
+            out.update(side)
         # A fraction above 1 means the arithmetic around a kernel is wrong (or the kernel is not doing the work it is priced for):
         # such a line is not printed.
         bad = [(n, r.get("kernel"), f) for n, r in (("roofline", roofline), ("int_roofline", int_roof)) if r
@@ -314,7 +327,7 @@ def main():
             out["pcie_inclusive_vs_cpu_all_cores"] = round(best / cpu["all_cores"]["value"], 1)
             out["pcie_inclusive_vs_cpu_all_cores_caveat"] = ("the CPU side is a C restatement of the Go reference, by its own note ~2-3x slower per core than the Go binary would be: "
                                                              "against the Go binary read this ratio as roughly a third to a half of what is printed")
-        if args.workload == "csv" and world == 1 and not e.devices and args.other_configs and args.cpu_rows > 0 and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ):
+        if args.full and args.workload == "csv" and world == 1 and not e.devices and args.other_configs and args.cpu_rows > 0 and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ):
             out["other_configs"] = other_configs(args)
         try:  # RCCL prints its version banner through C stdio: flush that first, the JSON line is the last one
             import ctypes
@@ -330,7 +343,6 @@ def main():
             dist.destroy_process_group()
     except Exception:  # noqa: BLE001
         pass
-    if any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ):
-        return  # under rocprofv3 the tool writes its files at normal interpreter exit
-    os._exit(0)  # nothing may print after the JSON line
+    # a normal interpreter exit (never os._exit): atexit handlers and the loaded libraries' destructors run, which is where tools
+    # that watch the process (rocprofv3 among them) write what they recorded; the JSON line above was flushed last
 

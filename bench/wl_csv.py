@@ -18,7 +18,7 @@ class CsvWorkload(Base):
         self.dbuf, self.csv_bytes, _ = stage_shard(e.lib, e.workload, self.row0, a.rows)
         self.nl = 1
 
-    def step(self, keep=False, buf=None, plans=None, dense=False):
+    def step(self, keep=False, buf=None, plans=None, dense=False, hold=False):
         lib = self.env.lib
         db, consumed, errs = lib.csv_parse(self.opts, self.cschema, buf if buf is not None else self.dbuf)
         res = lib.apply_chain(plans if plans is not None else self.plans, db)
@@ -42,8 +42,73 @@ class CsvWorkload(Base):
             s["fixed_bytes"], s["str_bytes"], s["nstr"] = fixed, strb, sum(1 for i in range(v.ncols) if v.cols[i].repr in (12, 13, 14, 15))
             s["out_rows"], s["out_bytes"] = res.transformed.nrows, res.transformed.payload_bytes()
             s["errors"] = len(errs) + len(res.errors)
+        if hold:  # --dump-outputs: the step's result is kept (not freed) for dump_outputs
+            self.release_held()
+            self.held = (res.transformed, db)
+            return
         res.transformed.free()
         db.free()  # devnull sink
+
+    def release_held(self):
+        for b in getattr(self, "held", None) or ():
+            b.free()
+        self.held = None
+
+    # --dump-outputs: a fixed, seeded sample of the output rows (every column of them) plus the kept rows' source indices in full
+    DUMP_SAMPLE_ROWS = 4096
+    DUMP_SEED = 20240601
+    DUMP_LIMIT_BYTES = 64 << 20
+
+    def dump_outputs(self, out_dir):
+        """Writes what the last timed step computed — the transformed batch a caller of parse + mask + filter receives — as
+        out_dir/<name>.npy in float64 / float32: kept_src_row (every kept row's input row), then for DUMP_SAMPLE_ROWS output rows
+        drawn with a fixed seed, per column <col>.values (64-bit integers as [high, low] 32-bit halves, so that nothing is rounded),
+        <col>.nanos, <col>.valid, and for text columns <col>.len + <col>.bytes (the cells' bytes, concatenated).  out_dir None:
+        only release the held result (ranks other than 0)."""
+        held = getattr(self, "held", None)
+        if held is None:
+            raise RuntimeError("--dump-outputs: the timed region held no result")
+        try:
+            if out_dir is None:
+                return
+            abi = self.env.abi
+            out = held[0].download()
+            arrays = {}
+            n = out.nrows
+            src = out.src_row if out.src_row is not None else np.arange(n, dtype=np.int32)
+            arrays["kept_src_row"] = np.asarray(src[:n], dtype=np.float64)
+            rng = np.random.default_rng(self.DUMP_SEED)
+            idx = np.sort(rng.choice(n, size=min(self.DUMP_SAMPLE_ROWS, n), replace=False)) if n else np.zeros(0, np.int64)
+            arrays["sample_rows"] = idx.astype(np.float64)
+            for c in out.cols:
+                name = "".join(ch if ch.isalnum() or ch in "_-" else "_" for ch in c.name)
+                if c.repr in abi.VAR_REPRS:
+                    off = np.asarray(c.offsets, dtype=np.int64)
+                    lo, hi = off[idx], off[idx + 1]
+                    arrays[name + ".len"] = (hi - lo).astype(np.float64)
+                    data = np.asarray(c.data, dtype=np.uint8)
+                    cells = [data[a:b] for a, b in zip(lo, hi)]
+                    arrays[name + ".bytes"] = (np.concatenate(cells) if cells else np.zeros(0, np.uint8)).astype(np.float32)
+                else:
+                    v = np.asarray(c.values)[:n][idx]
+                    if v.dtype.itemsize == 8 and v.dtype.kind in "iu":
+                        u = v.view(np.uint64)
+                        v = np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+                    elif v.dtype != np.float32:
+                        v = v.astype(np.float64)
+                    arrays[name + ".values"] = v
+                    if c.nanos is not None:
+                        arrays[name + ".nanos"] = np.asarray(c.nanos)[:n][idx].astype(np.float64)
+                if c.validity is not None:
+                    arrays[name + ".valid"] = np.asarray(c.validity)[:n][idx].astype(np.float32)
+            total = sum(a.nbytes for a in arrays.values())
+            if total > self.DUMP_LIMIT_BYTES:
+                raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, self.DUMP_LIMIT_BYTES))
+            os.makedirs(out_dir, exist_ok=True)
+            for k, a in arrays.items():
+                np.save(os.path.join(out_dir, k + ".npy"), a)
+        finally:
+            self.release_held()
 
     def rows(self):
         return self.state["parsed_rows"]
@@ -58,6 +123,7 @@ class CsvWorkload(Base):
         nl = len(e.devices)
         go, done = threading.Barrier(nl + 1), threading.Barrier(nl + 1)
         errs = []
+        hold = getattr(self, "hold_last", False)  # --dump-outputs: lane 0's last step (the first device's shard)
 
         def lane_main(k):
             try:
@@ -68,8 +134,8 @@ class CsvWorkload(Base):
                     self.step(buf=buf, plans=plans)
                 e.lib.synchronize()
                 go.wait()
-                for _ in range(steps):
-                    self.step(buf=buf, plans=plans)
+                for i in range(steps):
+                    self.step(buf=buf, plans=plans, hold=hold and k == 0 and i == steps - 1)
                 e.lib.synchronize()
                 done.wait()
             except Exception as ex:  # noqa: BLE001
@@ -96,6 +162,7 @@ class CsvWorkload(Base):
         nl = max(1, min(nlanes or a.lanes, steps, e.lib.lane_count()))
         go, done = threading.Barrier(nl + 1), threading.Barrier(nl + 1)
         lane_err = []
+        hold = getattr(self, "hold_last", False) and nlanes is None and host_bufs is None  # the headline's timed region only
 
         def lane_main(k):
             try:
@@ -111,7 +178,7 @@ class CsvWorkload(Base):
                 go.wait()
                 for i in range(steps):
                     if i % nl == k:
-                        self.step(buf=buf)
+                        self.step(buf=buf, hold=hold and i == steps - 1)
                 e.lib.synchronize()
                 done.wait()
             except Exception as ex:  # noqa: BLE001

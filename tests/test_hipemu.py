@@ -267,10 +267,43 @@ def test_bench_devices_mode_runs_end_to_end_on_fake_devices():
     env = dict(os.environ, TFGPU_TEST_EMU_LIB=so, HIPEMU_DEVICES="2")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--devices", "0,1", "--rows", "1536", "--steps", "2", "--passes", "1", "--warmup", "1", "--prof-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--devices", "0,1", "--rows", "1536", "--steps", "2", "--passes", "1", "--warmup", "1", "--prof-steps", "1",
                         "--cpu-rows", "0", "--other-configs", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 2 and d["process_model"]["devices"] == [0, 1] and d["process_model"]["row_range_shards"] == 2
     assert d["config"]["rows_per_pass"] == 1536 and d["value"] > 0 and "emulated" in d
     assert d["kernels"].get("csv_parse_regular") or d["kernels"].get("csv_parse_tiles_general") or d["kernels"].get("csv_parse_listed")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` line (no --full) carries the headline and no per-kernel / cpu_baseline blocks; --dump-outputs writes the last timed
+    step's output as float32 / float64 .npy within 64 MB, the same for the same arguments whatever the warm-up.  Structural, on the emulator."""
+    import json
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tools", "hipemu"))
+    import build as emu_build
+    so = emu_build.build()
+    env = dict(os.environ, TFGPU_TEST_EMU_LIB=so)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "HIPEMU_DEVICES"):
+        env.pop(k, None)
+    dumps = []
+    for warmup in ("1", "2"):
+        d_out = str(tmp_path / ("w" + warmup))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", "1536", "--steps", "2", "--passes", "1", "--warmup", warmup,
+                            "--dump-outputs", d_out], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["unit"] == "rows/s" and d["higher_is_better"] is True and d["dtype"] == "u8" and d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2
+        assert not {"kernels", "roofline", "cpu_baseline", "parity", "other_configs"} & set(d), sorted(d)
+        files = sorted(os.listdir(d_out))
+        arrays = {f: np.load(os.path.join(d_out, f)) for f in files}
+        assert all(f.endswith(".npy") and a.dtype in (np.float32, np.float64) for f, a in arrays.items())
+        assert sum(os.path.getsize(os.path.join(d_out, f)) for f in files) <= 64 << 20
+        kept = arrays["kept_src_row.npy"]
+        assert 0 < len(kept) < 1536 and np.all(np.diff(kept) > 0)
+        assert np.all(arrays["clientip.len.npy"] == 64)   # the mask's hex digest
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    assert all(np.array_equal(dumps[0][f], dumps[1][f], equal_nan=True) for f in dumps[0])

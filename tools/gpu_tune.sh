@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 i=0
 for setting in "$@"; do
   i=$((i+1))
-  env $setting timeout 300 python bench.py --workload $WL --steps 5 --passes 1 --warmup 2 --cpu-rows 0 --overlap-lanes 0 --pcie-steps 0 --other-configs 0 > "$OUT/tune_${WL}_$i.json" 2> "$OUT/tune_${WL}_$i.err"
+  env $setting timeout 300 python bench.py --full --workload $WL --steps 5 --passes 1 --warmup 2 --cpu-rows 0 --overlap-lanes 0 --pcie-steps 0 --other-configs 0 > "$OUT/tune_${WL}_$i.json" 2> "$OUT/tune_${WL}_$i.err"
   python - "$OUT/tune_${WL}_$i.json" "$setting" <<'PY' | tee -a "$OUT/tune_$WL.txt"
 import json, sys
 try:

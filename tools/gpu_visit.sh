@@ -59,7 +59,7 @@ tests() {
 bench() {  # workloads, extra args
   for w in $1; do
     name=${w// /_}
-    timeout 600 python bench.py --workload $w $2 > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "== bench $w rc=$?"; tail -c 200 "$OUT/bench_$name.err" | grep -v amdgpu.ids
+    timeout 600 python bench.py --full --workload $w $2 > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "== bench $w rc=$?"; tail -c 200 "$OUT/bench_$name.err" | grep -v amdgpu.ids
     keepjson "$OUT/bench_$name.json"; line "$OUT/bench_$name.json"
   done
 }
@@ -86,9 +86,9 @@ traffic() {  # HBM bytes per launch of the dominant kernels: FETCH_SIZE / WRITE_
 case $MODE in
   tests) tests "$1" ;;
   bench) bench "${1:-csv}" "$2" ;;
-  ab) for w in $2; do for v in 1 0; do echo "== $w $1=$v"; env $1=$v timeout 300 python bench.py --workload $w --steps 5 --passes 1 --warmup 2 $QUIET > "$OUT/ab_${w}_$v.json" 2>/dev/null; line "$OUT/ab_${w}_$v.json"; done; done ;;
+  ab) for w in $2; do for v in 1 0; do echo "== $w $1=$v"; env $1=$v timeout 300 python bench.py --full --workload $w --steps 5 --passes 1 --warmup 2 $QUIET > "$OUT/ab_${w}_$v.json" 2>/dev/null; line "$OUT/ab_${w}_$v.json"; done; done ;;
   ablate) V=""; [ "$1" = TFGPU_CSV_ABLATE ] && V="TFGPU_LIB_VARIANT=ablate"   # the CSV kernels' profiling branches exist only in the ablate build: tools/build_variant.sh ablate tf_csv.hip -DTF_CSV_ABLATE_BUILD=1 (before gpurun)
-    for a in $4; do env $V $1=$a timeout 120 python bench.py --workload $3 --steps 2 --passes 1 --warmup 1 --prof-steps 5 $QUIET 2>/dev/null | python -c "
+    for a in $4; do env $V $1=$a timeout 120 python bench.py --full --workload $3 --steps 2 --passes 1 --warmup 1 --prof-steps 5 $QUIET 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']; print('$1=$a', {n:round(k[n]['avg_ms'],4) for n in k if n=='$2'})" | tee -a "$OUT/ablate_$2.txt"; done ;;
   pmc) bash tools/gpu_pmc2.sh "$1" "$TAG/pmc_$1" "${2:-csv}" "${3:-2}" "$4"; cp "$OUT/pmc_$1/summary.txt" "$OUT/pmc_$1.txt" ;;
@@ -103,11 +103,11 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']; print('
     date +%s > "$OUT/t0"
     tests
     traffic
-    timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench_csv.json" 2> "$OUT/bench_csv.err"; echo "== csv (the driver's command line) rc=$?"; keepjson "$OUT/bench_csv.json"; line "$OUT/bench_csv.json"
+    timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_csv.json" 2> "$OUT/bench_csv.err"; echo "== csv (the driver's command line, --full) rc=$?"; keepjson "$OUT/bench_csv.json"; line "$OUT/bench_csv.json"
     bench "configs0" "--from-rows"
     bench "configs2 configs3 configs4 configs4d json sr sr_proto collapse debezium debezium_sr"
-    timeout 400 python bench.py --workload configs4 --sink debezium > "$OUT/bench_configs4_debezium.json" 2> "$OUT/bench_configs4_debezium.err"; echo "== configs4 --sink debezium rc=$?"; keepjson "$OUT/bench_configs4_debezium.json"; line "$OUT/bench_configs4_debezium.json"
-    timeout 400 python bench.py --workload collapse --toast 0.5 > "$OUT/bench_collapse_toast.json" 2> "$OUT/bench_collapse_toast.err"; echo "== collapse --toast 0.5 rc=$?"; keepjson "$OUT/bench_collapse_toast.json"; line "$OUT/bench_collapse_toast.json"
+    timeout 400 python bench.py --full --workload configs4 --sink debezium > "$OUT/bench_configs4_debezium.json" 2> "$OUT/bench_configs4_debezium.err"; echo "== configs4 --sink debezium rc=$?"; keepjson "$OUT/bench_configs4_debezium.json"; line "$OUT/bench_configs4_debezium.json"
+    timeout 400 python bench.py --full --workload collapse --toast 0.5 > "$OUT/bench_collapse_toast.json" 2> "$OUT/bench_collapse_toast.err"; echo "== collapse --toast 0.5 rc=$?"; keepjson "$OUT/bench_collapse_toast.json"; line "$OUT/bench_collapse_toast.json"
     stats "csv configs2 configs3 json sr debezium debezium_sr configs4d"
     echo "elapsed $(( $(date +%s) - $(cat $OUT/t0) )) s" ;;
   *) echo "unknown mode $MODE"; exit 2 ;;
