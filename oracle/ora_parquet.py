@@ -188,7 +188,9 @@ def _column(arr, leaf, typ):
             out.append(["float64", float(v)])
         else:  # BYTE_ARRAY / FIXED_LEN_BYTE_ARRAY: []byte → string under "string" / "utf8" (restore.go:222-229)
             b = v.encode() if isinstance(v, str) else bytes(v)
-            out.append(["string", b])
+            # under "any" the []byte is handed back as it is (restore.go:217-252 unmarshals only a string); read here: parquet-go
+            # hands a BYTE_ARRAY leaf over as []byte, as the "string" / "utf8" cases above assume
+            out.append(["bytes", b] if typ == "any" else ["string", b])
     return out
 
 

@@ -249,3 +249,62 @@ def test_native_queue_fullsize(tf, sr_events):
             it, i = items[k], r0 + k
             assert (it["id"], it["nextlsn"], it["kind"], it["schema"], it["table"]) == (i % 1000, i + 10, "insert", "db", "events")
             assert it["columnnames"] == ["a", "b", "id", "n", "s"] and it["columnvalues"][2] == i and it["columnvalues"][4] == 'row "%d" <%x>' % (i, i * 2654435761 & 0xFFFFFF)
+
+
+# ---- configs[3] from its real source format: the hits fixture's rows as one Parquet object ----
+
+@pytest.fixture(scope="module")
+def hits_pq(tf, hits):
+    """the hits fixture's rows parsed under hits_parquet.SCHEMA (`hitcolor` utf8: see tests/hits_parquet.py) and written as one SNAPPY
+    object of four row groups"""
+    pytest.importorskip("pyarrow")
+    import hits_parquet as hp
+    db, consumed, errs = tf.csv_parse(hits["opts"], hp.SCHEMA, hits["dbuf"])
+    assert consumed == hits["total"] and not errs and db.nrows == N
+    host = db.download()
+    db.free()
+    obj, held = hp.write(host, codec="SNAPPY", row_group_size=300007)
+    assert held.nrows == N
+    return dict(hp=hp, host=host, obj=obj)
+
+
+def _json_text(tf, db, plans):
+    """configs[3]'s chain + JSONEachRow over a device batch (freed here)"""
+    tr = tf.apply_chain(plans, db)
+    assert not tr.errors
+    out = tf.serialize(abi.FMT_CH_JSON_EACH_ROW, tr.transformed)
+    text = bytes(out.download())
+    out.free(); tr.transformed.free(); db.free()
+    return text
+
+
+def test_parquet_object_reads_as_the_csv_columns_fullsize(tf, hits_pq):
+    """2^20 rows under the user OutputSchema: the read equals the CSV parse as whole arrays (dtype, repr, validity, values, nanos)."""
+    from test_gpu_configs3 import columns_diff
+    db = tf.parquet_read(hits_pq["obj"], hits_pq["hp"].SCHEMA)
+    got = db.download()
+    db.free()
+    why = columns_diff(got, hits_pq["host"])
+    assert why is None, why
+
+
+def test_configs3_from_parquet_equals_resident_columns_fullsize(tf, hits_pq):
+    """JSONEachRow of (Parquet → chain) = JSONEachRow of (resident columns → chain), byte for byte; two half objects give the two
+    halves of that text."""
+    import hashlib
+    from bench.wl_configs3 import Configs3Workload
+    hp, host = hits_pq["hp"], hits_pq["host"]
+    plans = [tf.Transformer(t, c) for t, c in Configs3Workload.CH]
+    text = _json_text(tf, tf.parquet_read(hits_pq["obj"], hp.SCHEMA), plans)
+    whole = (hashlib.sha256(text).digest(), len(text))  # (a gigabyte of text: only digests are kept)
+    del text
+    text = _json_text(tf, tf.DeviceBatch.upload(host), plans)
+    assert (hashlib.sha256(text).digest(), len(text)) == whole, "Parquet -> chain differs from resident columns -> chain"
+    del text
+    h, total = hashlib.sha256(), 0
+    for a, e in ((0, N // 2), (N // 2, N)):
+        obj, _ = hp.write(rows_slice(host, a, e), codec="SNAPPY", row_group_size=200003)
+        text = _json_text(tf, tf.parquet_read(obj, hp.SCHEMA), plans)
+        h.update(text); total += len(text)
+        del text
+    assert (h.digest(), total) == whole, "the halves' texts are not the whole text's halves"

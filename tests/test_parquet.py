@@ -554,3 +554,53 @@ def test_pages_inflated_on_the_device_fullsize(tf, codec, monkeypatch):
     monkeypatch.setenv("TFGPU_PQ_DEVICE_INFLATE", "1")
     _inflate_cases(tf, codec, 60000, ({}, {"use_dictionary": False, "data_page_size": 2048}, {"data_page_version": "2.0", "row_group_size": 1500}, {"use_dictionary": False, "data_page_size": 1 << 22}),
                    ({"use_dictionary": False, "data_page_size": 1 << 24}, {"use_dictionary": False, "data_page_size": 100000, "data_page_version": "2.0"}, {}), 3)
+
+
+NARROW = {"int8": (-128, 127), "int16": (-32768, 32767), "int32": (-(1 << 31), (1 << 31) - 1), "uint8": (0, 255), "uint16": (0, 65535), "uint32": (0, (1 << 32) - 1)}
+
+
+@pytest.mark.parametrize("leaf", ["int32", "int64"])
+def test_integer_leaf_under_a_narrower_output_schema_type(tf, leaf):
+    """An INT32 / INT64 leaf read under a narrower integer DataType of a user OutputSchema is cast.ToIntNN / ToUintNN of its value
+    (restore.go:115-157): that type's repr and width, every in-range value — both ends included — through PLAIN, dictionary and
+    v2 pages, nulls kept; the oracle (ora_parquet) reads the same.  A value outside the type's range is refused by name: what cast
+    makes of it is not pinned."""
+    from oracle import ora_parquet as op
+    at = pa.int32() if leaf == "int32" else pa.int64()
+    lim = (-(1 << 31), (1 << 31) - 1) if leaf == "int32" else (-(1 << 63), (1 << 63) - 1)
+    targets = {t: (max(lo, lim[0]), min(hi, lim[1])) for t, (lo, hi) in NARROW.items() if (t, leaf) != ("int32", "int32")}
+    n = 3001
+    rng = np.random.default_rng(9)
+    cols = {}
+    for t, (lo, hi) in targets.items():
+        v = [int(x) for x in rng.integers(lo, hi, n, endpoint=True)]
+        v[:4] = [lo, hi, 0 if lo <= 0 else lo, hi - 1]
+        cols[t] = pa.array([None if i % 13 == 5 else x for i, x in enumerate(v)], at)
+    t_ = pa.table(cols)
+    schema = abi.Schema.of([[t, t] for t in targets])
+    for kw in (dict(use_dictionary=False), dict(use_dictionary=True), dict(data_page_version="2.0", data_page_size=1024, dictionary_pagesize_limit=512, compression="SNAPPY")):
+        buf = io.BytesIO()
+        pq.write_table(t_, buf, **kw)
+        data = buf.getvalue()
+        out = tf.parquet_read(data, schema).download()
+        ref = abi.batch_from_rows(schema, list(targets), op.read(data, [(t, t) for t in targets], ""))
+        for c in out.cols:
+            assert c.repr == abi._GOTYPE_REPR[c.name] == ref.col(c.name).repr and c.values.dtype == abi.REPR_NP[c.repr], (c.name, kw)
+            want = cols[c.name].to_pylist()
+            assert [bool(x) for x in c.validity] == [w is not None for w in want], (c.name, kw)
+            assert [int(x) for x, w in zip(c.values, want) if w is not None] == [w for w in want if w is not None], (c.name, kw)
+        assert abi.batch_rows(out) == abi.batch_rows(ref), kw
+    # out of range: one cell one past either end, in a PLAIN and in a dictionary page
+    for t, (lo, hi) in targets.items():
+        for bad in (lo - 1, hi + 1):
+            if not lim[0] <= bad <= lim[1]:
+                continue
+            for dict_ in (False, True):
+                vals = [1, 2, None, bad, 1] * 40
+                buf = io.BytesIO()
+                pq.write_table(pa.table({"ok": pa.array(range(len(vals)), at), "c": pa.array(vals, at)}), buf, use_dictionary=dict_)
+                with pytest.raises(tf.TfgpuError) as ei:
+                    tf.parquet_read(buf.getvalue(), abi.Schema.of([["ok", "int64"], ["c", t]]))
+                assert ei.value.code == tf.ERR_UNSUPPORTED and "column c:" in str(ei.value), (t, bad, str(ei.value))
+                with pytest.raises(NotImplementedError):
+                    op.read(buf.getvalue(), [("c", t)], "")

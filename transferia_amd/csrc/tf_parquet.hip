@@ -653,8 +653,11 @@ __device__ __forceinline__ uint32_t seg_value(const uint8_t *file, const Seg &s,
 // value can meet: float32 under "double" → float64; an int32 under "int64" → cast.ToInt64; an int32 / int64 under "uint64" →
 // cast.ToUint64 (a negative value does not cast: 0); an int64 under "timestamp" → ytschema.Timestamp(v).Time(): MICROseconds
 // whatever unit the file states; DATE (parseLogicalDate, reader_parquet.go:285-297) → time.Unix(0, 0).Add(24h * days).
-enum : int32_t { CV_SAME = 0, CV_DATE = 1, CV_TS_MICROS = 2, CV_I32_I64 = 3, CV_I32_U64 = 4, CV_I64_U64 = 5, CV_F32_F64 = 6 };
-struct FixedOut { void *values; int32_t *nanos; int32_t in_width, out_width, conv; };
+// CV_NARROW: an int32 under int8 / int16 / uint8 / uint16 / uint32, an int64 under those or int32 → cast.ToIntNN / ToUintNN: the
+// value, retyped, in the column's own width.  What cast makes of a value outside [lo, hi] is
+// not pinned here, so such a value fails the call with TFGPU_ERR_UNSUPPORTED naming its column (error word [1] = column + 1).
+enum : int32_t { CV_SAME = 0, CV_DATE = 1, CV_TS_MICROS = 2, CV_I32_I64 = 3, CV_I32_U64 = 4, CV_I64_U64 = 5, CV_F32_F64 = 6, CV_NARROW = 7 };
+struct FixedOut { void *values; int32_t *nanos; int32_t in_width, out_width, conv, col; int64_t lo, hi; };
 // what the object's own numbers may not exceed, checked where the values are read (the error word is read back at the sync)
 enum : uint32_t { PQE_DICT_INDEX = 1, PQE_TEXT_LENGTH = 2, PQE_HYBRID = 3, PQE_INFLATE = 4 };
 // DELTA_BINARY_PACKED / DELTA_LENGTH_BYTE_ARRAY pages: ONE WAVE per page walks its miniblocks in order; a miniblock's deltas are
@@ -1293,11 +1296,13 @@ __device__ __forceinline__ void pq_fixed_row(const uint8_t *file, uint64_t tail_
       case CV_I32_U64: v = (int32_t)v < 0 ? 0 : (uint64_t)(int32_t)v; break;
       case CV_I64_U64: v = (int64_t)v < 0 ? 0 : v; break;
       case CV_F32_F64: v = (uint64_t)__double_as_longlong((double)__uint_as_float((uint32_t)v)); break;
+      case CV_NARROW: { const int64_t x = o.in_width == 4 ? (int64_t)(int32_t)v : (int64_t)v; if (x < o.lo || x > o.hi) err[1] = (uint32_t)o.col + 1; break; }
       default: break;
     }
   }
   switch (o.out_width) {
     case 1: ((uint8_t *)o.values)[r] = (uint8_t)v; break;
+    case 2: ((uint16_t *)o.values)[r] = (uint16_t)v; break;
     case 4: ((uint32_t *)o.values)[r] = (uint32_t)v; break;
     default: ((uint64_t *)o.values)[r] = v;
   }
@@ -1630,7 +1635,7 @@ static int parquet_read_impl(const uint8_t *f, uint64_t len, const tfgpu_schema 
   }
   // ---- pass 1 (host): every column's segment tables ----
   struct ColPlan {
-    DColumn d; bool nil = false, optional = false, is_text = false, is_int96 = false; uint32_t width = 0; int32_t conv = CV_SAME, out_width = 0;
+    DColumn d; bool nil = false, optional = false, is_text = false, is_int96 = false; uint32_t width = 0; int32_t conv = CV_SAME, out_width = 0; int64_t lo = 0, hi = 0;
     std::vector<Seg> lev, val; std::vector<TextPage> tpages; std::vector<uint64_t> dict_at; std::vector<uint32_t> dict_off, dict_len, dict_n;  // dict_n: entries per chunk dictionary (fixed: by chunk; text: at the chunk's first entry)
     uint64_t ord = 0; size_t arena_at = 0; uint64_t slot0 = 0;
   };
@@ -1669,17 +1674,30 @@ static int parquet_read_impl(const uint8_t *f, uint64_t len, const tfgpu_schema 
     if (is_flba && (leaf.type_len <= 0 || leaf.type_len > (1 << 20))) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_parquet_read: column " + leaf.name + ": FIXED_LEN_BYTE_ARRAY length");
     P.width = leaf.type == T_BOOLEAN ? 1 : (leaf.type == T_INT32 || leaf.type == T_FLOAT) ? 4 : is_int96 ? 12 : is_flba ? (uint32_t)leaf.type_len : 8;
     P.out_width = (int32_t)P.width;
+    // an integer DataType narrower than the leaf: (repr, width, range) of CV_NARROW
+    auto narrow = [&](int repr, int32_t w, int64_t lo, int64_t hi) { d.repr = repr; P.conv = CV_NARROW; P.out_width = w; P.lo = lo; P.hi = hi; };
     switch (leaf.type) {
       case T_BOOLEAN: d.repr = TFGPU_R_BOOL; break;
       case T_INT32:
         if (is_date) { d.repr = TFGPU_R_TIME; P.conv = CV_DATE; P.out_width = 8; }
         else if (dtype == TFGPU_T_INT64) { d.repr = TFGPU_R_INT64; P.conv = CV_I32_I64; P.out_width = 8; }
         else if (dtype == TFGPU_T_UINT64) { d.repr = TFGPU_R_UINT64; P.conv = CV_I32_U64; P.out_width = 8; }
+        else if (dtype == TFGPU_T_INT8) narrow(TFGPU_R_INT8, 1, INT8_MIN, INT8_MAX);
+        else if (dtype == TFGPU_T_INT16) narrow(TFGPU_R_INT16, 2, INT16_MIN, INT16_MAX);
+        else if (dtype == TFGPU_T_UINT8) narrow(TFGPU_R_UINT8, 1, 0, UINT8_MAX);
+        else if (dtype == TFGPU_T_UINT16) narrow(TFGPU_R_UINT16, 2, 0, UINT16_MAX);
+        else if (dtype == TFGPU_T_UINT32) narrow(TFGPU_R_UINT32, 4, 0, INT32_MAX);
         else d.repr = TFGPU_R_INT32;
         break;
       case T_INT64:
         if (dtype == TFGPU_T_TIMESTAMP) { d.repr = TFGPU_R_TIME; P.conv = CV_TS_MICROS; }
         else if (dtype == TFGPU_T_UINT64) { d.repr = TFGPU_R_UINT64; P.conv = CV_I64_U64; }
+        else if (dtype == TFGPU_T_INT8) narrow(TFGPU_R_INT8, 1, INT8_MIN, INT8_MAX);
+        else if (dtype == TFGPU_T_INT16) narrow(TFGPU_R_INT16, 2, INT16_MIN, INT16_MAX);
+        else if (dtype == TFGPU_T_INT32) narrow(TFGPU_R_INT32, 4, INT32_MIN, INT32_MAX);
+        else if (dtype == TFGPU_T_UINT8) narrow(TFGPU_R_UINT8, 1, 0, UINT8_MAX);
+        else if (dtype == TFGPU_T_UINT16) narrow(TFGPU_R_UINT16, 2, 0, UINT16_MAX);
+        else if (dtype == TFGPU_T_UINT32) narrow(TFGPU_R_UINT32, 4, 0, UINT32_MAX);
         else d.repr = TFGPU_R_INT64;
         break;
       case T_FLOAT: if (dtype == TFGPU_T_FLOAT64) { d.repr = TFGPU_R_FLOAT64; P.conv = CV_F32_F64; P.out_width = 8; } else d.repr = TFGPU_R_FLOAT32; break;
@@ -2046,7 +2064,7 @@ static int parquet_read_impl(const uint8_t *f, uint64_t len, const tfgpu_schema 
       if (d.repr == TFGPU_R_TIME) d.nanos = P.conv == CV_TS_MICROS ? dalloc((size_t)nrows * 4) : dalloc_zero((size_t)nrows * 4);
       fd.push_back(FixedDesc{reinterpret_cast<const Seg *>(B + q.val_at), (int32_t)P.val.size(), 0, rank_of.count(q.oc) ? rank_of[q.oc] : nullptr,
                              P.dict_at.empty() ? nullptr : reinterpret_cast<const uint64_t *>(B + q.dict_at_at), P.dict_n.empty() ? nullptr : reinterpret_cast<const uint32_t *>(B + q.dict_n_at),
-                             FixedOut{d.values->p, P.conv == CV_TS_MICROS ? ptr<int32_t>(d.nanos) : nullptr, (int32_t)P.width, P.out_width, P.conv}});
+                             FixedOut{d.values->p, P.conv == CV_TS_MICROS ? ptr<int32_t>(d.nanos) : nullptr, (int32_t)P.width, P.out_width, P.conv, (int32_t)q.oc, P.lo, P.hi}});
     }
     size_t ti = 0;
     for (auto &q : text_cols) {
@@ -2108,6 +2126,7 @@ static int parquet_read_impl(const uint8_t *f, uint64_t len, const tfgpu_schema 
   clk.at("columns enqueued");
   tf::sync();  // ONE wait for the text columns' sizes (a dictionary-coded column can be far longer than its chunk), then the copies
   clk.at("first sync");
+  if (!herr[0] && herr[1]) return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_parquet_read: column " + plans[herr[1] - 1].d.name + ": a value outside the range of its DataType (what cast.ToIntNN / ToUintNN makes of it is not pinned)");
   if (herr[0]) return tf::fail(TFGPU_ERR_INVALID, herr[0] == PQE_DICT_INDEX ? "tfgpu_parquet_read: a dictionary index past its dictionary" : herr[0] == PQE_INFLATE ? "tfgpu_parquet_read: malformed SNAPPY / LZ4_RAW page (an element that runs past its page, or a copy from in front of it)" : herr[0] == PQE_HYBRID ? "tfgpu_parquet_read: malformed dictionary indices (an RLE / bit-packed run that ends outside its page)" : "tfgpu_parquet_read: a byte-array length that runs past its page");
   for (size_t k = 0; k < totals.size(); k++) if (((uint64_t)htot64w[2 * k] | (uint64_t)htot64w[2 * k + 1] << 32) >= 0xFFFFFFF0ull) return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_parquet_read: column " + plans[totals[k]].d.name + " holds 4 GiB of text or more: read the object row group by row group");
   if (!totals.empty()) {

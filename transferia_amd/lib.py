@@ -177,16 +177,18 @@ def lane_device(lane: int) -> int:
     return int(d.value)
 
 
-def parquet_read(data: bytes, schema: Optional[abi.Schema] = None, ns: str = "", table: str = "", file_name: Optional[str] = None) -> "DeviceBatch":
-    """ReaderParquet.Read's decode on the device: a whole Parquet object (host bytes) → one device batch.  With file_name the
-    schema's `__file_name` / `__row_index` are the reader's system columns (constructCI)."""
+def parquet_read(data, schema: Optional[abi.Schema] = None, ns: str = "", table: str = "", file_name: Optional[str] = None) -> "DeviceBatch":
+    """ReaderParquet.Read's decode on the device: a whole Parquet object (host bytes or a pinned HostBuffer) → one device batch.  With
+    file_name the schema's `__file_name` / `__row_index` are the reader's system columns (constructCI)."""
     init()
+    if isinstance(data, DeviceBuffer):
+        raise TypeError("parquet_read: an object already in HBM is read by parquet_read_staged")
     out = C.c_void_p()
-    buf = np.frombuffer(data, dtype=np.uint8)
+    ptr_, n, _mem, keep = _bytes_arg(data)
     cs = schema.to_c() if schema is not None else None
     L = load()
     L.tfgpu_parquet_read_object.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
-    _check(L.tfgpu_parquet_read_object(C.c_void_p(buf.ctypes.data), C.c_uint64(len(buf)), abi.MEM_HOST, C.byref(cs) if cs is not None else None, ns.encode(), table.encode(),
+    _check(L.tfgpu_parquet_read_object(C.c_void_p(ptr_), C.c_uint64(n), abi.MEM_HOST, C.byref(cs) if cs is not None else None, ns.encode(), table.encode(),
                                        file_name.encode() if file_name is not None else None, C.byref(out)))
     return DeviceBatch(out)
 
