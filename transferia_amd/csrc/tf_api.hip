@@ -175,7 +175,7 @@ int tfgpu_apply(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, tf
   if (!in || !out || (nplans > 0 && !plans)) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply: null argument");
   std::lock_guard<std::mutex> lk(ctx().mu);
   ApplyCtx ax;
-  std::unique_ptr<tfgpu_dbatch> cur = std::make_unique<tfgpu_dbatch>(*in);
+  std::unique_ptr<tfgpu_dbatch> cur = tf::snapshot(*in);  // (another lane may be making the handle dense: copied under that transition's lock)
   // transformation.do (transformation.go:252-274): toApply = t.Apply(toApply).Transformed
   std::vector<std::vector<int>> hopped;
   const std::vector<int> seq = chain_sequence(plans, nplans, &hopped);  // a filter_rows in front of the mask_fields it does not read

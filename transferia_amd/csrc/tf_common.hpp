@@ -95,7 +95,7 @@ struct Context {
   struct Pending { int idx; hipEvent_t a, b; int64_t units = 0; };
   std::vector<Pending> pending;
   std::vector<hipEvent_t> free_events;
-  hipEvent_t dense_event = nullptr;  // re-recorded behind every selection -> dense gather of this lane while other lanes are alive (tf::dense_locked)
+  hipEvent_t dense_event = nullptr;  // re-recorded behind every selection -> dense gather of this lane while other lanes are alive (tf::dense_locked); destroyed with the lane
   std::mutex mu;  // serialises API calls that enqueue on the stream
   int num_cus = 256;
   std::shared_ptr<struct DevMem> pow10tab;  // math.Pow10(n), n = -323..308 (tf_json.hip)
@@ -207,6 +207,10 @@ void materialize(const struct ::tfgpu_dbatch &b, const std::vector<const DColumn
 void dense(const struct ::tfgpu_dbatch *b, bool absent_ok = false);
 void dense_locked(const struct ::tfgpu_dbatch &b);
 int lanes_created();   // lanes (stream + cache + pinned ring) this process has made so far (tf_runtime.hip)
+uint64_t lane_generation();  // counts tfgpu_shutdown calls: what a lane owned (tfgpu_dbatch::dense_done) died with an older generation (tf_runtime.hip)
+// a copy of `b` taken under the selection -> dense transition's lock: either still the selection (its own reference to the PendingRows) or the
+// gathered columns, never half of each — what a caller works from when another lane may make `b` dense meanwhile
+std::unique_ptr<struct ::tfgpu_dbatch> snapshot(const struct ::tfgpu_dbatch &b);
 bool has_absent(const struct ::tfgpu_dbatch &b);
 // a fresh bitmap: (validity, or all ones when null) with the bits of `absent` cleared — an ABSENT cell reads nil (tf_runtime.hip)
 Buf validity_minus_absent(const Buf &validity, const Buf &absent, int64_t nrows);
@@ -233,7 +237,8 @@ struct tfgpu_dbatch {
   std::vector<tf::DColumn> cols;                    // EMPTY while `pending` is set
   std::shared_ptr<tf::PendingRows> pending;         // set: this batch is nrows selected rows of pending->src, not gathered yet
   void *dense_done = nullptr;                       // the gathering lane's hipEvent_t (Context::dense_event, lives as long as the lane), recorded behind the gather that ended
-  int dense_lane = -1;                              //   `pending` while several lanes were alive: a reader on ANOTHER lane's stream waits for it (tf::dense)
+  int dense_lane = -1;                              //   `pending`: a reader on ANOTHER lane's stream waits for it (tf::dense) ...
+  uint64_t dense_gen = 0;                           //   ... while the lanes of that tfgpu_init are alive (tf::lane_generation: the event dies in tfgpu_shutdown, behind a stream sync)
   std::vector<tf::DColumn> replaced;                // with `pending`: columns already computed over the kept rows (dense, by name)
   std::vector<std::pair<std::string, int>> schema;  // TableSchema (name, DataType) in order; empty = same as cols
   std::vector<std::string> key_names;               // names of the PrimaryKey columns of that schema (MakeMapKeys)

@@ -3,6 +3,7 @@
 // stream; device memory comes from a stream-ordered pool whose release
 // threshold is unlimited, so steady-state batches never hit hipMalloc.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "tf_common.hpp"
@@ -22,6 +23,9 @@ static thread_local int g_lane = 0;
 static std::vector<int> g_devices;      // the process's device list; lane k -> g_devices[k % size]
 static std::vector<int> g_device_cus;   // multiProcessorCount of each
 static std::mutex g_init_mu;
+static std::atomic<int> g_lane_count{0};        // lanes alive (tf::lanes_created)
+static std::atomic<uint64_t> g_generation{1};  // +1 at every tfgpu_shutdown: events of the lanes that died there are not waited on
+uint64_t lane_generation() { return g_generation.load(std::memory_order_acquire); }
 static int lane_device_index(int lane) { return g_devices.empty() ? 0 : lane % (int)g_devices.size(); }
 #define g_ctx g_lanes[0]
 
@@ -58,7 +62,15 @@ int bind_lane(int lane) {
   if (lane < 0 || lane >= MAX_LANES) throw Error(TFGPU_ERR_INVALID, "lane out of range");
   std::lock_guard<std::mutex> lk(g_init_mu);
   if (!g_ctx) throw Error(TFGPU_ERR_DEVICE, "tfgpu_init() has not been called");
-  if (!g_lanes[lane]) g_lanes[lane] = make_lane(lane);
+  if (!g_lanes[lane]) {
+    g_lanes[lane] = make_lane(lane);
+    g_lane_count.fetch_add(1);
+    // A selection made dense while this lane did not exist left no event behind its gather (tf::dense_locked records one only when lanes_created() > 1):
+    // the lane is counted first, then every older lane's stream is drained, so whatever was queued without an event is complete before this lane reads it.
+    // (Every bind_lane of every thread waits behind g_init_mu for that drain: lanes are made a few times in a process's life.)
+    for (int i = 0; i < MAX_LANES; i++)
+      if (i != lane && g_lanes[i]) { ensure_device(g_lanes[i]->device); TF_HIP(hipStreamSynchronize(g_lanes[i]->stream)); }
+  }
   ensure_device(g_lanes[lane]->device);
   const int prev = g_lane;
   g_lane = lane;
@@ -73,6 +85,7 @@ static void destroy_lane(std::unique_ptr<Context> &c) {
   hipStreamSynchronize(c->stream);
   for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (auto e : c->free_events) hipEventDestroy(e);
+  if (c->dense_event) hipEventDestroy(c->dense_event);  // (the stream was synchronised above: every gather it stood behind is complete)
   c->pow10tab.reset();
   c->consts.clear();
   c->blocks.trim();
@@ -254,7 +267,7 @@ __global__ void upload_validity_minus_absent(const uint8_t *validity_in, const u
   validity_out[i] = (uint8_t)((validity_in ? validity_in[i] : 0xFFu) & ~absent[i]);
 }
 
-int lanes_created() { int n = 0; for (auto &l : g_lanes) if (l) n++; return n; }
+int lanes_created() { return g_lane_count.load(); }
 Buf validity_minus_absent(const Buf &validity, const Buf &absent, int64_t nrows) {
   const int64_t nb = (nrows + 7) / 8;
   Buf v = dalloc((size_t)nb + 8);
@@ -320,6 +333,7 @@ int tfgpu_init_devices(const int *devices, int ndevices) {
     }
   t_device = -1;  // (the loop may have left another device current)
   g_ctx = make_lane(0);
+  g_lane_count.store(1);
   return TFGPU_OK;
   TF_API_END
 }
@@ -329,7 +343,9 @@ int tfgpu_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_init_mu);
   if (!g_ctx) return TFGPU_OK;
   executor_shutdown();  // the push workers hold lanes
+  g_generation.fetch_add(1, std::memory_order_acq_rel);  // a batch that outlives this call never waits on a destroyed dense_event (wait_dense_nolock)
   for (int i = MAX_LANES - 1; i >= 0; i--) destroy_lane(g_lanes[i]);
+  g_lane_count.store(0);
   g_lane = 0;
   t_device = -1;
   g_devices.clear(); g_device_cus.clear();

@@ -6,6 +6,8 @@
 // them is a contraction, so there is no MFMA here; mask is INT32-ALU bound
 // (2–3 SHA-256 compressions per value), everything else is HBM bound.
 #include <algorithm>
+#include <chrono>
+#include <thread>
 
 #include "tf_devfmt.hpp"
 #include "tf_devfloat.hpp"
@@ -214,7 +216,7 @@ __global__ void fill_offsets_stride_kernel(uint32_t *off, int64_t n, uint32_t st
 static std::unique_ptr<tfgpu_dbatch> shallow_copy(const tfgpu_dbatch &in) { return std::make_unique<tfgpu_dbatch>(in); }
 
 // what apply_mask refuses for a whole batch, before anything is computed
-void mask_precheck(const tfgpu_plan &p, const tfgpu_dbatch &in) {
+void mask_precheck(const tfgpu_plan &p, const tfgpu_dbatch &in) {  // (`in`: the caller's own copy, as apply_plan's)
   for (auto &c : (in.pending ? in.pending->src->cols : in.cols)) {
     if (!p.mask_has(c.name)) continue;
     bool done = false;
@@ -254,6 +256,7 @@ std::vector<int> chain_sequence(const tfgpu_plan *const *plans, int n, std::vect
   return seq;
 }
 
+// `in`: a batch nobody else changes meanwhile (apply_plan)
 static std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch &in) {
   auto out = shallow_copy(in);
   for (auto &sc : out->schema) if (p.mask_has(sc.first)) sc.second = TFGPU_T_UTF8;  // hmac_hasher.go:35-46
@@ -779,12 +782,34 @@ static std::unique_ptr<tfgpu_dbatch> compact(const tfgpu_dbatch &in, Buf keep /*
 
 // The selection → dense transition mutates a handle its callers hold as const, and one handle can be reached from two threads on two lanes (the
 // Bufferer's collector concatenating a batch the pusher is serializing): the lane's mutex is the CALLING thread's, so the transition has a lock of
-// its own, and with more than one lane alive the gather is complete — not merely queued on the gathering lane's stream — when the lock is released
-// (the next reader may sit on another stream).  ADVICE r5.
+// its own (g_dense_mu: every read of `pending` / `replaced` / the columns of a handle that may still change happens under it, or on a snapshot()
+// taken under it).  When the lock is released the gather is only QUEUED on the gathering lane's stream, with the lane's dense_event recorded behind
+// it whenever a second lane exists; a lane made later synchronises the older lanes' streams as it is made (bind_lane), which covers the gathers
+// queued while it did not exist.  Every other way into the dense columns — dense()'s first check, and the caller that lost the race and finds
+// `pending` gone in dense_locked() — makes its own stream wait for that event before it returns.
+// ADVICE r5, r6; tests/test_gpu_lane_handover.py.
 static std::mutex g_dense_mu;
+// TFGPU_DENSE_HOLD_MS=n (tests only, read once): a caller that has SEEN a selection (dense()) or copied one (snapshot()) sleeps n ms on the host before
+// it goes on, with no lock held — two lanes that read one handle at the same moment then both see `pending`, one gathers, and the other certainly arrives behind it
+// (tests/test_gpu_lane_handover.py).  Unset: nothing.
+static void dense_hold() {
+  static const int ms = [] { const char *e = std::getenv("TFGPU_DENSE_HOLD_MS"); return e ? std::atoi(e) : 0; }();
+  if (ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(ms));
+}
+// a batch another lane made dense: this lane's stream waits for that gather (no-op on the gathering lane, and once that lane is gone: tfgpu_shutdown
+// synchronised its stream before it destroyed the event)
+static void wait_dense_nolock(const tfgpu_dbatch &b) {
+  if (b.dense_done && b.dense_lane != current_lane() && b.dense_gen == lane_generation()) TF_HIP(hipStreamWaitEvent(ctx().stream, (hipEvent_t)b.dense_done, 0));
+}
+std::unique_ptr<tfgpu_dbatch> snapshot(const tfgpu_dbatch &b) {
+  std::unique_ptr<tfgpu_dbatch> c;
+  { std::lock_guard<std::mutex> dl(g_dense_mu); c = std::make_unique<tfgpu_dbatch>(b); }
+  if (c->pending) dense_hold();  // (tests: the copy is held while another lane gathers the handle it was taken from)
+  return c;
+}
 void dense_locked(const tfgpu_dbatch &b) {
   std::lock_guard<std::mutex> dl(g_dense_mu);
-  if (!b.pending) return;
+  if (!b.pending) { wait_dense_nolock(b); return; }  // another lane gathered since the caller looked: its kernels may still be queued there
   tfgpu_dbatch &mb = const_cast<tfgpu_dbatch &>(b);  // (the handle's observable value does not change: the same rows, now gathered)
   std::shared_ptr<PendingRows> pr = b.pending;
   std::unique_ptr<tfgpu_dbatch> g = gather_batch(*pr->src, pr->sel, b.nrows, b.replaced.empty() ? nullptr : &b.replaced);
@@ -792,18 +817,18 @@ void dense_locked(const tfgpu_dbatch &b) {
   mb.kind = g->kind; mb.src_row = g->src_row; mb.part_id = g->part_id;
   mb.replaced.clear();
   if (lanes_created() > 1) {  // the gather is QUEUED on this lane's stream: leave an event behind it for readers on other streams (a host sync here cost configs[4] 0.2 ms a pass)
-    // ONE event a lane, recorded again at every transition: a reader that waits on a later record than its batch's waits for more than it must, never for less
+    // ONE event a lane, recorded again at every transition: a reader that waits on a later record than its batch's waits for more than it must, never for less.
+    // With one lane alive nothing is recorded (an event behind every transition cost the single-lane configs[4] line 6-10 % — one box, one visit,
+    // two runs each: 670 / 638 M rows/s against 712 / 711 M): a lane made later is
+    // counted FIRST and then waits for every older lane's stream (bind_lane), so a gather queued before this line saw it is complete before it reads.
     Context &cx = ctx();
     if (!cx.dense_event) TF_HIP(hipEventCreateWithFlags(&cx.dense_event, hipEventDisableTiming));
     TF_HIP(hipEventRecord(cx.dense_event, cx.stream));
     mb.dense_done = (void *)cx.dense_event;
     mb.dense_lane = current_lane();
+    mb.dense_gen = lane_generation();
   }
   mb.pending.reset();
-}
-// a batch another lane made dense: this lane's stream waits for that gather (no-op on the gathering lane, or once nobody else is alive)
-static void wait_dense_nolock(const tfgpu_dbatch &b) {
-  if (b.dense_done && b.dense_lane != current_lane()) TF_HIP(hipStreamWaitEvent(ctx().stream, (hipEvent_t)b.dense_done, 0));
 }
 bool has_absent(const tfgpu_dbatch &b) {
   std::lock_guard<std::mutex> dl(g_dense_mu);
@@ -820,6 +845,7 @@ void dense(const tfgpu_dbatch *b, bool absent_ok) {
   if (!b) return;
   if (!absent_ok) refuse_absent(*b);
   { std::lock_guard<std::mutex> dl(g_dense_mu); if (!b->pending) { wait_dense_nolock(*b); return; } }
+  dense_hold();
   std::lock_guard<std::mutex> lk(ctx().mu);
   dense_locked(*b);
 }
@@ -1820,8 +1846,10 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
   // the column droppers and the row filters carry the bitmaps.  `sql` (it serializes whole rows for clickhouse-local) and batches whose rows carry
   // their own name ORDER (col_order indexes the column list these transformers change) stay with the stock path.
   if (p.kind == PK_SQL || (in.col_order && p.kind != PK_SHARDER)) refuse_absent(in);
-  if (in.pending && (p.kind != PK_MASK || has_absent(in))) dense_locked(in);
-  else if (!in.pending) { std::lock_guard<std::mutex> dl(g_dense_mu); wait_dense_nolock(in); }  // (the callers hold the lane's mutex) only mask_field reads through a selection
+  // `in` is the caller's OWN copy of the handle it was given (tfgpu_apply and push_run take it with snapshot(), under the transition's lock): nobody
+  // else changes it.  A copy taken after another lane made the handle dense carries that lane's event: this lane's stream waits for it here.
+  if (in.pending && (p.kind != PK_MASK || has_absent(in))) dense_locked(in);  // only mask_field reads through a selection
+  else if (!in.pending) { std::lock_guard<std::mutex> dl(g_dense_mu); wait_dense_nolock(in); }  // (the callers hold the lane's mutex)
   switch (p.kind) {
     case PK_MASK: return apply_mask(p, in);
     case PK_RENAME: return apply_rename(p, in);

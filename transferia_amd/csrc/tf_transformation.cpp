@@ -87,7 +87,7 @@ static void push_run(tfgpu_transformation &t, const tfgpu_dbatch &in, const tfgp
   const auto t0 = std::chrono::steady_clock::now();
   const std::vector<int> plan = table_plan(t, in.ns, in.table, schema_of(in, schema));
   std::lock_guard<std::mutex> lk(ctx().mu);
-  std::unique_ptr<tfgpu_dbatch> cur = std::make_unique<tfgpu_dbatch>(in);
+  std::unique_ptr<tfgpu_dbatch> cur = snapshot(in);  // (another lane may be making the handle dense: copied under that transition's lock)
   std::vector<const tfgpu_plan *> chain;
   for (int pi : plan) chain.push_back(t.transformers[(size_t)pi]);
   std::vector<std::vector<int>> hopped;

@@ -161,6 +161,14 @@ def init(device: Optional[int] = None) -> int:
     return device
 
 
+def shutdown():
+    """tfgpu_shutdown: every lane's stream is synchronised and destroyed; handles made before it must not be read afterwards.
+    The next init() binds the process again."""
+    global _initialised
+    _check(load().tfgpu_shutdown())
+    _initialised = None
+
+
 def init_devices(devices) -> List[int]:
     """Bind this process to several GPUs: lane k lives on devices[k % len(devices)] (one worker process driving the node)."""
     global _initialised
