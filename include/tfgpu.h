@@ -225,6 +225,10 @@ typedef enum tfgpu_rowerr {
                                       receiver (receiver.go:60-96, receiver_engine.go:108-146)                          */
   TFGPU_ROW_SR_PROTO = 25,         /* confluent SR protobuf: the schema text does not compile, or the message bytes do not unmarshal (format_protobuf.go:44-53) */
   TFGPU_ROW_DROPPED = 24,          /* registry-framed Debezium: an earlier event of the same Kafka message failed; DoBuf stops there */
+  TFGPU_ROW_NGINX_FORMAT = 26,     /* nginx: a format literal does not match the line, or a variable's delimiter is not found
+                                    * (nginx_format.go parseEntry)                                                       */
+  TFGPU_ROW_NGINX_EXTRA = 27,      /* nginx: unconsumed non-white-space behind the last token under
+                                    * NginxUnexpectedFieldBehaviorError (reader_nginx_funcs.go checkUnexpectedFields)    */
   TFGPU_ROW_DBZ_FIELD = 23         /* a schema field is missing from before / after, or receiveField rejects its value
                                       (receiver.go:216-230, receiver_engine.go:148-287)                                 */
 } tfgpu_rowerr;
@@ -649,6 +653,51 @@ int tfgpu_csv_parse(const tfgpu_csv_options *opts, const tfgpu_schema *schema, c
  * double quotes (its three states reduce to the parity of the '"' seen so far).  *row_ends = uint32 offsets one past the
  * '\n' of every complete entry, in order (a tfgpu_dbuf of *nrows words); what follows the last one is the io.EOF remainder. */
 int tfgpu_csv_split_rows(const void *bytes, uint64_t len, int mem, tfgpu_dbuf **row_ends, int64_t *nrows);
+
+/* ---- nginx access-log ingest: s3 reader registry "nginx" (pkg/providers/s3/reader/registry/nginx) ------------------
+ * A log_format string is compiled once per source into a token program (literals and $variables, nginx_format.go
+ * tokenizeFormat / compileFormat); tfgpu_nginx_parse walks it over every line of a chunk on the device (parseEntry), converts
+ * the fields the schema's columns read (convertNginxValue, constructCI, strictify.Strictify) and returns the batch.
+ * tfgpu_nginx_format_* and tfgpu_nginx_resolve_schema are host code and need no GPU. */
+typedef struct tfgpu_nginx_format tfgpu_nginx_format;
+/* TFGPU_ERR_CONFIG: no tokens, or no variable (compileFormat's two errors) */
+int tfgpu_nginx_format_compile(const char *log_format, tfgpu_nginx_format **out);
+void tfgpu_nginx_format_free(tfgpu_nginx_format *f);
+int tfgpu_nginx_format_ntokens(const tfgpu_nginx_format *f);
+/* token i: *is_variable and its Value (the name without '$', or the literal text); the string lives as long as f */
+int tfgpu_nginx_format_token(const tfgpu_nginx_format *f, int i, int *is_variable, const char **value);
+int tfgpu_nginx_format_nfields(const tfgpu_nginx_format *f);
+/* field i's unique column name (a repeated variable gets _2, _3, ...); NULL out of range */
+const char *tfgpu_nginx_format_field(const tfgpu_nginx_format *f, int i);
+/* NewNginxSchemaResolver (nginx_schema_resolver.go:52-101): output_schema NULL or without columns = the compiled schema (every
+ * field a utf8 string, Path = its index, OriginalType "nginx:utf8"); otherwise its columns, a missing Path taken from the field of
+ * the same name (a column without Path and without such a field is dropped), a missing OriginalType = "nginx:<DataType>".
+ * Unless hide_system_cols, __file_name and __row_index are put in front, as keys when no column is one.  Free with
+ * tfgpu_schema_free. */
+int tfgpu_nginx_resolve_schema(const tfgpu_nginx_format *f, const tfgpu_schema *output_schema, int hide_system_cols, tfgpu_schema **out);
+
+typedef struct tfgpu_nginx_options {
+  const char *file_name;          /* value of __file_name; NULL = ""                                              */
+  uint64_t row_number_base;       /* lineCounter of the chunk's first non-blank line (reader_nginx.go: 1)         */
+  uint8_t hide_system_cols;       /* both system columns are nil                                                  */
+  uint8_t unexpected_field_error; /* NginxUnexpectedFieldBehaviorError; 0 = Ignore / Unspecified                  */
+  uint8_t last_chunk;             /* lastRound: a tail without '\n' is a line                                     */
+} tfgpu_nginx_options;
+void tfgpu_nginx_options_default(tfgpu_nginx_options *o);  /* row_number_base = 1 */
+
+/* Parse the complete lines of `len` bytes (`bytes` / `mem` as tfgpu_csv_parse; text columns are views into the chunk the same
+ * way).  Column i of `schema` reads field atoi(Path) (not an integer: TFGPU_ERR_CONFIG); an index no field has gives
+ * DefaultValue; a bare "-" is nil for every type; date / datetime columns parse "02/Jan/2006:15:04:05 -0700"; everything else is
+ * the string through Strictify.  *consumed = one past the last '\n' (len with last_chunk; 0 and an empty batch when there is no
+ * '\n').  Blank lines (TrimRight "\r", then Unicode TrimSpace) are skipped and do not count; *next_row_number = lineCounter
+ * behind the chunk.  A failed line is left out of the batch and reported: row = its lineCounter, code = TFGPU_ROW_NGINX_FORMAT /
+ * TFGPU_ROW_NGINX_EXTRA (column -1) or TFGPU_ROW_CAST / TFGPU_ROW_RANGE / TFGPU_ROW_HOST_FALLBACK with the column. */
+int tfgpu_nginx_parse(const tfgpu_nginx_format *f, const tfgpu_nginx_options *opts, const tfgpu_schema *schema,
+                      const void *bytes, uint64_t len, int mem, tfgpu_dbatch **out, uint64_t *consumed,
+                      uint64_t *next_row_number, tfgpu_row_error *errs, int64_t errs_cap, int64_t *nerrs);
+/* the token walk's geometry: bytes of a line tile staged in LDS (a longer line is walked from HBM) and lines per workgroup */
+int tfgpu_nginx_tile_bytes(void);
+int tfgpu_nginx_workgroup_lines(void);
 
 /* ---- JSON / TSKV ingest: parsers/generic GenericParser{Format:"json" | "tskv"} ----------- */
 /* generic.AuxParserOpts (pkg/parsers/generic/generic_parser.go:40-77) as the "json" parser

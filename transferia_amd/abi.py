@@ -37,7 +37,8 @@ COL_KEY, COL_REQUIRED, COL_FAKE_KEY = 1, 2, 4
 ROWERR = {0: "OK", 1: "UNSUPPORTED_KIND", 2: "COLUMN_NOT_FOUND", 3: "INT_OVERFLOW", 4: "TYPE_PAIR", 5: "MISSING_CELL",
           6: "CAST", 7: "RANGE", 8: "QUOTE", 9: "DOUBLE_QUOTE", 10: "QUOTING_DISABLED", 11: "HOST_FALLBACK",
           12: "JSON_SYNTAX", 13: "PARSE_VAL", 14: "NIL_KEY", 15: "SR_SHORT", 16: "SR_MAGIC", 17: "SR_TYPE", 18: "SR_REQUIRED",
-          19: "DBZ_UNPACK", 20: "DBZ_PAYLOAD", 21: "DBZ_OP", 22: "DBZ_SCHEMA", 23: "DBZ_FIELD", 24: "DROPPED", 25: "SR_PROTO"}
+          19: "DBZ_UNPACK", 20: "DBZ_PAYLOAD", 21: "DBZ_OP", 22: "DBZ_SCHEMA", 23: "DBZ_FIELD", 24: "DROPPED", 25: "SR_PROTO",
+          26: "NGINX_FORMAT", 27: "NGINX_EXTRA"}
 ROWERR_ID = {v: k for k, v in ROWERR.items()}
 for _k, _v in ROWERR.items():
     globals()["ROW_" + _v] = _k
@@ -123,6 +124,11 @@ class CCsvOptions(C.Structure):
                 ("decimal_point", C.c_char_p), ("skip_rows", C.c_int64),
                 ("file_name", C.c_char_p), ("row_number_base", C.c_uint64), ("hide_system_cols", C.c_uint8),
                 ("encoding_table", C.POINTER(C.c_uint32))]
+
+
+class CNginxOptions(C.Structure):
+    _fields_ = [("file_name", C.c_char_p), ("row_number_base", C.c_uint64), ("hide_system_cols", C.c_uint8),
+                ("unexpected_field_error", C.c_uint8), ("last_chunk", C.c_uint8)]
 
 
 class CJsonOptions(C.Structure):

@@ -32,6 +32,8 @@ EXPORTS = [
     "tfgpu_transformation_get_stats", "tfgpu_executor_start", "tfgpu_transformation_push_async", "tfgpu_wait", "tfgpu_collapse", "tfgpu_keys_changed", "tfgpu_dbatch_deepsizeof", "tfgpu_partition", "tfgpu_comm_unique_id", "tfgpu_comm_init", "tfgpu_comm_destroy", "tfgpu_comm_rank", "tfgpu_comm_world", "tfgpu_exchange", "tfgpu_csv_options_default", "tfgpu_csv_parse", "tfgpu_csv_split_rows", "tfgpu_json_parse", "tfgpu_json_result_schema", "tfgpu_sr_frames", "tfgpu_sr_json_parse", "tfgpu_sr_compile_schema", "tfgpu_sr_schema_info", "tfgpu_sr_schema_free", "tfgpu_sr_compile_proto", "tfgpu_pb_schema_info", "tfgpu_pb_schema_free", "tfgpu_sr_proto_parse", "tfgpu_debezium_unpack", "tfgpu_debezium_unpack_cached", "tfgpu_debezium_parse", "tfgpu_debezium_compile_schema", "tfgpu_dbz_schema_info", "tfgpu_dbz_schema_free", "tfgpu_dbz_receiver_create", "tfgpu_dbz_receiver_destroy", "tfgpu_dbz_receiver_known", "tfgpu_dbz_receive", "tfgpu_dbz_receive_group", "tfgpu_dbz_receive_group_meta", "tfgpu_debezium_compile_registry_schema", "tfgpu_dbz_receiver_add_registry_schema", "tfgpu_debezium_registry_frames", "tfgpu_dbz_receive_registry", "tfgpu_serialize", "tfgpu_serialize_ex", "tfgpu_serialize_batch", "tfgpu_ch_native_block", "tfgpu_queue_serialize", "tfgpu_queue_raw_column", "tfgpu_queue_mirror", "tfgpu_queue_part_groups", "tfgpu_kafka_hash_partition", "tfgpu_kafka_partitions", "tfgpu_debezium_emit", "tfgpu_dbuf_size", "tfgpu_dbuf_ptr",
     "tfgpu_dbuf_download", "tfgpu_dbuf_free", "tfgpu_dbuf_upload", "tfgpu_dbuf_alloc", "tfgpu_dbuf_write", "tfgpu_prof_enable", "tfgpu_prof_reset", "tfgpu_prof_count",
     "tfgpu_prof_get", "tfgpu_prof_get_units", "tfgpu_parquet_read_object", "tfgpu_parquet_staging_size", "tfgpu_parquet_read_staged", "tfgpu_parquet_resolve_schema", "tfgpu_dbatch_nrows", "tfgpu_dbatch_dense",
+    "tfgpu_nginx_format_compile", "tfgpu_nginx_format_free", "tfgpu_nginx_format_ntokens", "tfgpu_nginx_format_token", "tfgpu_nginx_format_nfields", "tfgpu_nginx_format_field",
+    "tfgpu_nginx_resolve_schema", "tfgpu_nginx_options_default", "tfgpu_nginx_parse", "tfgpu_nginx_tile_bytes", "tfgpu_nginx_workgroup_lines",
 ]
 
 
@@ -137,6 +139,19 @@ def load():
     L.tfgpu_dbatch_nrows.restype = C.c_int64
     L.tfgpu_dbatch_nrows.argtypes = [C.c_void_p]
     L.tfgpu_dbatch_dense.argtypes = [C.c_void_p]
+    L.tfgpu_nginx_format_compile.argtypes = [C.c_char_p, C.POINTER(P)]
+    L.tfgpu_nginx_format_free.argtypes = [P]
+    L.tfgpu_nginx_format_free.restype = None
+    L.tfgpu_nginx_format_ntokens.argtypes = [P]
+    L.tfgpu_nginx_format_token.argtypes = [P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+    L.tfgpu_nginx_format_nfields.argtypes = [P]
+    L.tfgpu_nginx_format_field.argtypes = [P, C.c_int]
+    L.tfgpu_nginx_format_field.restype = C.c_char_p
+    L.tfgpu_nginx_resolve_schema.argtypes = [P, C.POINTER(abi.CSchema), C.c_int, C.POINTER(C.POINTER(abi.CSchema))]
+    L.tfgpu_nginx_options_default.argtypes = [C.POINTER(abi.CNginxOptions)]
+    L.tfgpu_nginx_options_default.restype = None
+    L.tfgpu_nginx_parse.argtypes = [P, C.POINTER(abi.CNginxOptions), C.POINTER(abi.CSchema), P, C.c_uint64, C.c_int, C.POINTER(P), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64), C.POINTER(abi.CRowError), C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -828,6 +843,85 @@ def csv_parse(opts: abi.CCsvOptions, schema, data, max_errors: int = 1 << 16):
     el = [(int(errs[i].row), abi.ROWERR.get(int(errs[i].code), str(errs[i].code)), int(errs[i].step), int(errs[i].column))
           for i in range(min(int(nerr.value), max_errors))]
     return DeviceBatch(out), int(consumed.value), el
+
+
+class NginxFormat:
+    """A compiled nginx log_format (compileFormat, pkg/providers/s3/reader/registry/nginx/nginx_format.go): host code, no GPU needed.
+    Raises TfgpuError(ERR_CONFIG) for a format without tokens or without a variable."""
+
+    def __init__(self, log_format: str):
+        L = load()
+        self._h = C.c_void_p()
+        _check(L.tfgpu_nginx_format_compile(log_format.encode("utf-8"), C.byref(self._h)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            load().tfgpu_nginx_format_free(h)
+
+    @property
+    def tokens(self):
+        """[(is_variable, value bytes)]"""
+        L = load()
+        out = []
+        for i in range(L.tfgpu_nginx_format_ntokens(self._h)):
+            isv, val = C.c_int(0), C.c_char_p()
+            _check(L.tfgpu_nginx_format_token(self._h, i, C.byref(isv), C.byref(val)))
+            out.append((bool(isv.value), val.value))
+        return out
+
+    @property
+    def fields(self) -> List[str]:
+        L = load()
+        return [L.tfgpu_nginx_format_field(self._h, i).decode("utf-8") for i in range(L.tfgpu_nginx_format_nfields(self._h))]
+
+    def resolve_schema(self, output_schema: Optional[abi.Schema] = None, hide_system_cols: bool = False) -> abi.Schema:
+        """NewNginxSchemaResolver: the TableSchema the reader works with"""
+        L = load()
+        out = C.POINTER(abi.CSchema)()
+        cs = output_schema.to_c() if output_schema is not None and output_schema.cols else None
+        _check(L.tfgpu_nginx_resolve_schema(self._h, C.byref(cs) if cs is not None else None, 1 if hide_system_cols else 0, C.byref(out)))
+        try:
+            return abi.Schema.from_c(out.contents)
+        finally:
+            L.tfgpu_schema_free(out)
+
+
+def nginx_options(file_name: str = "", row_number_base: int = 1, hide_system_cols: bool = False, unexpected_field_error: bool = False,
+                  last_chunk: bool = False) -> abi.CNginxOptions:
+    o = abi.CNginxOptions()
+    load().tfgpu_nginx_options_default(C.byref(o))
+    o.file_name = file_name.encode("utf-8")
+    o.row_number_base, o.hide_system_cols = row_number_base, 1 if hide_system_cols else 0
+    o.unexpected_field_error, o.last_chunk = 1 if unexpected_field_error else 0, 1 if last_chunk else 0
+    return o
+
+
+def nginx_tile():
+    """(bytes of lines the token walk stages in LDS at a time, lines per workgroup)"""
+    L = load()
+    return int(L.tfgpu_nginx_tile_bytes()), int(L.tfgpu_nginx_workgroup_lines())
+
+
+def nginx_parse(fmt: NginxFormat, opts: abi.CNginxOptions, schema, data, max_errors: int = 1 << 16):
+    """NginxReader.Read's parse of one chunk on the device.  `data` is bytes, a pinned HostBuffer or a DeviceBuffer.
+    Returns (DeviceBatch, consumed_bytes, next_row_number, errors)."""
+    init()
+    L = load()
+    cs = schema if isinstance(schema, abi.CSchema) else schema.to_c()
+    out, consumed, nxt, nerr = C.c_void_p(), C.c_uint64(0), C.c_uint64(0), C.c_int64(0)
+    errs = _errbuf(max_errors)
+    if isinstance(data, DeviceBuffer):
+        p, n, mem = data.ptr, data.size, abi.MEM_DEVICE
+    elif isinstance(data, HostBuffer):
+        p, n, mem = data.ptr, data.size, abi.MEM_HOST
+    else:
+        buf = np.frombuffer(data, dtype=np.uint8)
+        p, n, mem = (buf.ctypes.data if len(buf) else None), len(buf), abi.MEM_HOST
+    _check(L.tfgpu_nginx_parse(fmt._h, C.byref(opts), C.byref(cs), p, n, mem, C.byref(out), C.byref(consumed), C.byref(nxt), errs, max_errors, C.byref(nerr)))
+    el = [(int(errs[i].row), abi.ROWERR.get(int(errs[i].code), str(errs[i].code)), int(errs[i].step), int(errs[i].column))
+          for i in range(min(int(nerr.value), max_errors))]
+    return DeviceBatch(out), int(consumed.value), int(nxt.value), el
 
 
 def csv_split_rows(data) -> np.ndarray:
