@@ -440,7 +440,28 @@ int tfgpu_host_free(void *p);
  * empty string's (= the constant k2) — a shared misreading of the 17-32 /
  * 33-64 / > 64-byte branches would not be caught here.  Row-wise expressions
  * are where the device subset ends: aggregates, joins and several
- * statements stay with the stock transformer.                                */
+ * statements stay with the stock transformer.
+ * "regex_replace_transformer" (pkg/transformer/registry/regex_replace/
+ * transformer.go; config keys regexMatch, replaceRule, columns, tables) has a
+ * device plan for a subset of Go's RE2 syntax, matched leftmost-first like Go:
+ * literals (UTF-8), \ + punctuation, \t \n \r \f \v \xHH, `.`, [...] with
+ * ranges, negation and \d \w \s, \d \D \w \W \s \S, * + ? {n} {n,} {n,m}
+ * greedy and lazy, (...) and (?:...), |, ^ $ \A \z \b \B (no flags: $ is
+ * the end of the text).  Anything else — flag groups, named groups, \p{..},
+ * \C, \Q..\E, [[:..:]], a literal U+FFFD, a * + {n,} whose body can match the
+ * empty string, a pattern over the TFGPU_REGEX_* caps below — answers
+ * TFGPU_ERR_UNSUPPORTED naming the construct; what Go's compiler rejects
+ * answers TFGPU_ERR_CONFIG ("unable to compile match regexp: ...").  Either
+ * way the shim keeps the stock transformer.  replaceRule is Regexp.Expand's
+ * template ($1, ${1}, $$; names expand to nothing).  It is not one of the ten
+ * names tfgpu_registry_* lists (below).                                     */
+#define TFGPU_REGEX_MAX_PROG 128    /* instructions a pattern may compile to (repeats {n,m} are unrolled)      */
+#define TFGPU_REGEX_MAX_RANGES 256  /* (lo, hi) rune pairs of all its character classes together               */
+#define TFGPU_REGEX_MAX_GROUPS 16   /* capturing groups                                                         */
+#define TFGPU_REGEX_MAX_RULE 1024   /* bytes of replaceRule                                                     */
+#define TFGPU_REGEX_MAX_CELL (1 << 20) /* bytes of one text cell: a batch that holds a longer one in a rewritten column answers
+                                        * TFGPU_ERR_UNSUPPORTED at tfgpu_apply, as does a cell whose searches take more than
+                                        * (length + 1) * (program size + 16) + 1024 steps (a pattern that is quadratic in Go too) */
 int tfgpu_plan_create(const char *type_name, const char *config_json, tfgpu_plan **out);
 void tfgpu_plan_destroy(tfgpu_plan *plan);
 const char *tfgpu_plan_type(const tfgpu_plan *plan);                /* Type()        */
@@ -452,7 +473,9 @@ int tfgpu_plan_suitable(const tfgpu_plan *plan, const char *table_ns, const char
 int tfgpu_plan_result_schema(const tfgpu_plan *plan, const tfgpu_schema *in, tfgpu_schema **out);
 void tfgpu_schema_free(tfgpu_schema *s);
 
-/* Number of registered transformer types and their names.                   */
+/* The first ten device transformer types and their names (mask_field ... sql).  The list is kept as it was first
+ * published; types that got a device plan later (regex_replace_transformer) are not in it: tfgpu_plan_create is the
+ * authority on whether a type has a device plan.                                                                    */
 int tfgpu_registry_count(void);
 const char *tfgpu_registry_name(int i);
 

@@ -561,10 +561,15 @@ std::unique_ptr<tfgpu_plan> make_plan(const std::string &type_name, const std::s
     p->tables = tables_of(cfg); p->columns.init({}, {});
     p->sql_query = cfg.s("query");
     sql_parse(p->sql_query, *p);
+  } else if (type_name == "regex_replace_transformer") {  // regex_replace/transformer.go:17-49
+    p->kind = PK_REGEX_REPLACE;
+    p->tables = tables_of(cfg); p->columns = columns_of(cfg);
+    p->rx_pattern = cfg.s("regexMatch"); p->rx_rule = cfg.s("replaceRule");
+    p->rx = std::make_shared<const RegexProg>(regex_compile(p->rx_pattern, p->rx_rule));
   } else if (type_name == "lambda" || type_name == "dbt" || type_name == "logger" || type_name == "yt_dict_transformer" || type_name == "raw_doc_grouper" ||
              type_name == "raw_cdc_doc_grouper" || type_name == "table_splitter_transformer" || type_name == "number_to_float_transformer" ||
              type_name == "problem_item_detector" || type_name == "batch_splitter" || type_name == "filter_strm_access_log" || type_name == "jsonparser" ||
-             type_name == "regex_replace_transformer" || type_name == "filter_rows_by_ids" || type_name == "mongo_pk_extender") {
+             type_name == "filter_rows_by_ids" || type_name == "mongo_pk_extender") {
     // registered in the reference (pkg/transformer/registry/*), outside the device subset (out of scope)
     throw Error(TFGPU_ERR_UNSUPPORTED, "transformer type " + type_name + " has no device plan: keep it on the host");
   } else {
@@ -626,6 +631,7 @@ bool plan_suitable(const tfgpu_plan &p, const std::string &ns, const std::string
     }
     case PK_SQL:  // clickhouse_local.go:335-349: the table filter decides; a result without columns / key is only warned about
       return p.tables.match_table(ns, name);
+    case PK_REGEX_REPLACE: return p.tables.match(name);  // transformer.go:64-66: the table's name alone, no namespace variants
     case PK_TO_DATETIME:  // to_datetime.go:63-76
       if (!p.tables.match_table(ns, name)) return false;
       if (p.columns.empty()) return false;
@@ -661,6 +667,10 @@ std::string plan_description(const tfgpu_plan &p) {
     case PK_TO_DATETIME:
       if (p.columns.empty()) return "Transform to datetime uint32 column values";
       return "Transform to datetime uint32 column values (include: " + trim100(join(p.columns.include_src, "|")) + ", exclude: " + trim100(join(p.columns.exclude_src, "|")) + ")";
+    case PK_REGEX_REPLACE:  // transformer.go:72-80
+      if (p.columns.empty()) return "Replace all string column values via regular expression";
+      return "Replace given string column values (include: " + trim100(join(p.columns.include_src, "|")) + ", exclude: " + trim100(join(p.columns.exclude_src, "|")) +
+             ") via regular expression `" + p.rx_pattern + "`";
     case PK_REPLACE_PK: return "Replace primary keys to: " + join_keys(p.new_keys) + " ";
     case PK_SHARDER:
       if (p.columns.empty()) return "Transform to shard tables by field values";

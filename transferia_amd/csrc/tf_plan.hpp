@@ -58,7 +58,7 @@ std::vector<FTerm> parse_filter(const std::string &src);  // throws Error(TFGPU_
 
 }  // namespace tf
 
-enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL };
+enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL, PK_REGEX_REPLACE };
 
 namespace tf {
 // ---- `sql` transformer, device subset (tf_sql.cpp) ----------------------------------------------------------------------
@@ -84,6 +84,23 @@ struct SqlOut {  // one result column over a concrete input schema
   int64_t ival = 0; std::string sval; std::vector<SqlOp> ops;
   int root = -1;  // SQL_EXPR
 };
+// ---- regex_replace_transformer (tf_regex.hip): the RE2 subset of include/tfgpu.h compiled to a bounded program --------------------
+enum RxOp : uint32_t { RX_CHAR, RX_CLASS, RX_ANY, RX_ANYNOTNL, RX_SPLIT, RX_JMP, RX_SAVE, RX_ASSERT, RX_MATCH };
+enum RxAssert : uint32_t { RXA_BEGIN_TEXT, RXA_END_TEXT, RXA_WORD_BOUNDARY, RXA_NO_WORD_BOUNDARY };
+struct RxInst { uint32_t op, x, y, c; };  // x: next pc (SPLIT: the preferred branch); y: SPLIT's other branch / CLASS's first range pair; c: rune / pair count / slot / RxAssert
+struct RxSeg { int32_t group; uint32_t off, len; };  // one piece of the compiled replaceRule: group >= 0 copies that group, else lits[off, off+len)
+struct RegexProg {
+  std::vector<RxInst> inst;
+  std::vector<uint32_t> ranges;  // (lo, hi) rune pairs of every class, back to back
+  uint32_t start = 0;
+  int ngroups = 0;               // capturing groups of the pattern
+  int nslots = 2;                // 2 * (1 + highest group the rule reads): groups the rule never reads are not recorded
+  std::vector<RxSeg> segs;
+  std::string lits;
+};
+// throws Error(TFGPU_ERR_CONFIG, "unable to compile match regexp: ...") for what Go rejects, Error(TFGPU_ERR_UNSUPPORTED, naming the construct) for
+// what lies outside the subset
+RegexProg regex_compile(const std::string &pattern, const std::string &rule);
 }  // namespace tf
 
 struct tfgpu_plan {
@@ -112,6 +129,9 @@ struct tfgpu_plan {
   std::vector<tf::SqlNode> sql_nodes;  // expression trees of SQL_EXPR items and of a general WHERE
   int sql_where_root = -1;             // >= 0: the WHERE is this tree (`exprs` is empty then)
   int sql_where_tree = -1;             // the WHERE's tree whatever its shape (a UInt64 column sends the filter_rows form to it too: sql_where_as_tree)
+  // regex_replace_transformer
+  std::string rx_pattern, rx_rule;
+  std::shared_ptr<const tf::RegexProg> rx;
   // replace_primary_key
   std::vector<std::string> new_keys;
   bool is_new_key(const std::string &n) const {
@@ -146,7 +166,12 @@ struct ApplyCtx {
   std::vector<tfgpu_row_error> errs;
   int step = 0;
 };
+// NOT for PK_REGEX_REPLACE (it throws `unknown plan kind`): chains go through apply_step below.  The one direct caller left replays mask_field
+// plans only (tf_transformation.cpp, the hopped masks).  A further plan kind belongs into apply_plan itself, with the profile stamp of
+// tf_transform.hip refreshed (tests/test_profiles_stamp.py), not into a third dispatcher.
 std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
+// apply_plan for the kinds tf_transform.hip runs, regex_replace_transformer through tf_regex.hip: what tfgpu_apply and the Push loop call per step
+std::unique_ptr<tfgpu_dbatch> apply_step(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
 void mask_precheck(const tfgpu_plan &p, const tfgpu_dbatch &in);  // throws what apply_mask would refuse for the whole batch
 std::vector<int> chain_sequence(const tfgpu_plan *const *plans, int n, std::vector<std::vector<int>> *hopped);  // see tf_transform.hip
 }  // namespace tf
