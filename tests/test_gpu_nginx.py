@@ -101,10 +101,36 @@ def test_cdn_lines_typed(tf, oracle):
 
 
 def test_timestamp_column_is_a_plain_string(tf, oracle):
-    """parse_cell's CSV-only integer shortcut does not apply: "1700000000" under `timestamp` is what cast.ToTimeE makes of the string"""
+    """the CSV reader's integer shortcut (parse_cell) does not apply: "1700000000" under `timestamp` is what cast.ToTimeE makes of the string"""
     schema = abi.Schema([abi.ColSchema("t", "timestamp", False, "0"), abi.ColSchema("u", "timestamp", False, "1")])
     data = b"1700000000 2024-05-06T07:08:09Z\n2024-05-06 2024-05-06 07:08:09\n- 20240506\n"
     run_both(tf, oracle, "$a $b", schema, data)
+
+
+# one value per layout of spf13/cast's StringToDate list, in its order (a zone abbreviation is UTC: Go gives any other one a fabricated zero offset) ...
+CAST_LAYOUT_CELLS = [
+    "2024-05-06", "2024-05-06T07:08:09+02:00", "2024-05-06T07:08:09", "Mon, 06 May 2024 07:08:09 +0200", "Mon, 06 May 2024 07:08:09 UTC",
+    "06 May 24 07:08 +0200", "06 May 24 07:08 UTC", "Monday, 06-May-24 07:08:09 UTC", "2024-05-06 07:08:09.123456789 +0000 UTC",
+    "2024-05-06T07:08:09+0200", "2024-05-06 07:08:09+0200", "2024-05-06 07:08:09", "Mon May  6 07:08:09 2024", "Mon May  6 07:08:09 UTC 2024",
+    "Mon May 06 07:08:09 +0200 2024", "2024-05-06 07:08:09+02:00", "06 May 2024", "2024-05-06 07:08:09 +02:00", "2024-05-06 07:08:09 +0200",
+    "7:08PM", "May  6 07:08:09", "May  6 07:08:09.123", "May  6 07:08:09.123456", "May  6 07:08:09.123456789"]
+# ... and the shapes the fixed-shape fast path in front of that list (parse_datetime, tf_strictcell.hpp) decides by itself
+FAST_PATH_CELLS = [
+    "2024-05-06T07:08:09.5", "2024-05-06T07:08:09,5", "2024-05-06 07:08:09.25", "2024-05-06 07:08:09,25", "2024-05-06T07:08:09.1234567891234Z",
+    "2024-05-06T07:08:09Z", "2024-05-06T07:08:09.5+02:00", "2024-05-06T07:08:09-05:30", "2024-05-06T07:08:09+25:00", "2024-05-06T7:08:09", "2024-05-06 7:08:09",
+    "2023-02-30", "2024-02-29", "2024-05-06T24:00:00", "2024-05-06T07:08:60", "2024-05-06T07:08:09 Z", "2024-05-06 07:08:09 Z", "2024-05-06 07:08:09Z", "-", ""]
+
+
+def test_timestamp_cells_take_the_fast_path_and_every_cast_layout(tf, oracle):
+    """a `timestamp` cell is cast.ToTimeE of the string: the fixed shapes through the fast path, everything else through the 24 layouts, and both
+    say what oracle.strictify says (run_both also asserts that no line is a HOST_FALLBACK row of the oracle)"""
+    cells = CAST_LAYOUT_CELLS + FAST_PATH_CELLS
+    data = "".join('"%s"\n' % c for c in cells).encode()
+    _, out, want = run_both(tf, oracle, '"$t"', abi.Schema([abi.ColSchema("t", "timestamp", False, "0")]), data)
+    # Go's range rules: an offset hour above 24, a day the month does not have, hour 24, second 60; a space in front of "Z" and "" fit no layout
+    bad = ["2024-05-06T07:08:09+25:00", "2023-02-30", "2024-05-06T24:00:00", "2024-05-06T07:08:60", "2024-05-06T07:08:09 Z", "2024-05-06 07:08:09 Z", ""]
+    assert want.errors == [(1 + cells.index(c), "CAST", 0) for c in bad] and len(want.rows) == len(cells) - len(bad)
+    assert list(want.rows[0]) == [("time", (1714953600, 0))] and list(want.rows[1]) == [("time", (1714972089, 0))], want.rows[:2]
 
 
 # ---- 3. shapes where the kernel can go wrong ---------------------------------------------------------------------------------

@@ -32,6 +32,7 @@
 #include "tf_gotime.hpp"
 #include "tf_f64range.hpp"
 #include "tf_plan.hpp"
+#include "tf_strictcell.hpp"
 
 // TFGPU_CSV_ABLATE=n (leave a kernel after phase n; results are NOT valid) is a profiling build only: the product's kernels carry none of
 // its branches (`if (CSV_ABL(t) == 31)` sat in every integer cell of the one kernel that is instruction-bound).
@@ -210,18 +211,6 @@ template <class F> __device__ __forceinline__ int sanitize(const CsvOpts &o, con
 // ---------------------------------------------------------------------------
 // typed parsers over a Field range [a,b)
 // ---------------------------------------------------------------------------
-// spf13/cast trimZeroDecimal: "12.00" → "12"
-template <class F> __device__ __forceinline__ uint32_t trim_zero_decimal(const F &f, uint32_t a, uint32_t b) {
-  bool found_zero = false;
-  for (uint32_t i = b; i > a; i--) {
-    uint32_t c = f[i - 1];
-    if (c == '.') { if (found_zero) return i - 1; }
-    else if (c == '0') found_zero = true;
-    else return b;
-  }
-  return b;
-}
-
 template <class F> __device__ __forceinline__ bool field_equals(const F &f, uint32_t a, uint32_t b, const uint8_t *s, uint32_t n) {
   if (b - a != n) return false;
   for (uint32_t i = 0; i < n; i++) if (f[a + i] != s[i]) return false;
@@ -235,74 +224,13 @@ template <class F> __device__ __forceinline__ bool in_list(const CsvOpts &o, int
   return false;
 }
 
-// cast.StringToDate (spf13/cast v1.7.1 timeFormats) for the fixed numeric shapes:
-//   2006-01-02 | 2006-01-02T15:04:05[.frac][Z07:00] | 2006-01-02 15:04:05[.frac]
-// returns 0 ok, TFGPU_ROW_CAST if the shape is one of these but the value is
-// invalid, TFGPU_ROW_HOST_FALLBACK if the text has another shape.
-template <class F> __device__ int parse_datetime(const F &f, uint32_t a, uint32_t b, int64_t *sec, int32_t *nsec) {
-  uint32_t n = b - a;
-  if (n < 10) return TFGPU_ROW_HOST_FALLBACK;
-  for (int i = 0; i < 10; i++) {
-    uint32_t c = f[a + i];
-    if (i == 4 || i == 7) { if (c != '-') return TFGPU_ROW_HOST_FALLBACK; } else if (!dg(c)) return TFGPU_ROW_HOST_FALLBACK;
-  }
-  int64_t y = (f[a] - '0') * 1000 + (f[a + 1] - '0') * 100 + (f[a + 2] - '0') * 10 + (f[a + 3] - '0');
-  int mo = (f[a + 5] - '0') * 10 + (f[a + 6] - '0'), d = (f[a + 8] - '0') * 10 + (f[a + 9] - '0');
-  int h = 0, mi = 0, se = 0; int64_t ns = 0; int off = 0;
-  if (n > 10) {
-    uint32_t sep = f[a + 10];
-    if (sep != 'T' && sep != ' ') return TFGPU_ROW_HOST_FALLBACK;
-    uint32_t k = a + 11;
-    // stdHour "15" takes one or two digits; minutes/seconds are fixed two digits
-    if (k >= b || !dg(f[k])) return TFGPU_ROW_HOST_FALLBACK;
-    h = f[k] - '0'; k++;
-    if (k < b && dg(f[k])) { h = h * 10 + (f[k] - '0'); k++; }
-    if (k + 6 > b || f[k] != ':' || !dg(f[k + 1]) || !dg(f[k + 2]) || f[k + 3] != ':' || !dg(f[k + 4]) || !dg(f[k + 5])) return TFGPU_ROW_HOST_FALLBACK;
-    mi = (f[k + 1] - '0') * 10 + (f[k + 2] - '0'); se = (f[k + 4] - '0') * 10 + (f[k + 5] - '0');
-    k += 6;
-    if (k + 1 < b && (f[k] == '.' || f[k] == ',') && dg(f[k + 1])) {
-      k++; int nd = 0;
-      while (k < b && dg(f[k])) { if (nd < 9) { ns = ns * 10 + (f[k] - '0'); nd++; } k++; }
-      while (nd < 9) { ns *= 10; nd++; }
-    }
-    if (k < b) {
-      if (sep != 'T') return TFGPU_ROW_HOST_FALLBACK;  // "… 15:04:05 -0700", "…Z07:00" after a space: host path
-      if (f[k] == 'Z' && k + 1 == b) k++;
-      else if ((f[k] == '+' || f[k] == '-') && k + 6 == b && dg(f[k + 1]) && dg(f[k + 2]) && f[k + 3] == ':' && dg(f[k + 4]) && dg(f[k + 5])) {
-        int hh = (f[k + 1] - '0') * 10 + (f[k + 2] - '0'), mm = (f[k + 4] - '0') * 10 + (f[k + 5] - '0');
-        if (hh > 24 || mm > 60) return TFGPU_ROW_CAST;
-        off = (f[k] == '-' ? -1 : 1) * (hh * 3600 + mm * 60);
-        k += 6;
-      } else return TFGPU_ROW_HOST_FALLBACK;
-    }
-  }
-  if (mo < 1 || mo > 12 || d < 1 || d > dev::days_in_month(mo, y) || h > 23 || mi > 59 || se > 59) return TFGPU_ROW_CAST;
-  *sec = dev::days_from_civil(y, mo, d) * 86400 + h * 3600 + mi * 60 + se - off;
-  *nsec = (int32_t)ns;
-  return 0;
-}
-
-// castx.ToJSONNumberE acceptance (fastfloat.Parse grammar or ParseInt base 10)
-template <class F> __device__ bool json_number_ok(const F &f, uint32_t a, uint32_t b) {
-  if (a >= b) return false;
-  uint32_t p = a;
-  if (f[p] == '-' || f[p] == '+') p++;
-  uint32_t d0 = p; while (p < b && dg(f[p])) p++;
-  uint32_t nd = p - d0; bool ok = true;
-  if (p < b && f[p] == '.') { p++; uint32_t f0 = p; while (p < b && dg(f[p])) p++; if (p == f0) nd = 0; else nd += p - f0; }
-  if (nd > 0 && p < b && (f[p] == 'e' || f[p] == 'E')) { p++; if (p < b && (f[p] == '-' || f[p] == '+')) p++; uint32_t x0 = p; while (p < b && dg(f[p])) p++; if (p == x0) ok = false; }
-  if (ok && nd > 0 && p == b) return true;
-  // inf / infinity / nan, case-insensitive
-  uint32_t q = a; if (f[q] == '-' || f[q] == '+') q++;
-  uint32_t n = b - q;
-  auto ci = [&](const char *s, uint32_t sl) { if (n != sl) return false; for (uint32_t i = 0; i < sl; i++) if (lower_(f[q + i]) != (uint32_t)s[i]) return false; return true; };
-  return ci("inf", 3) || ci("infinity", 8) || ci("nan", 3);
-}
-
 // ---------------------------------------------------------------------------
 // cell parse: constructCI / getCorrespondingValue / Strictify for ONE mapped column
 // ---------------------------------------------------------------------------
-enum CsvKind : int32_t { CK_INT, CK_UINT, CK_STR, CK_JSONNUM, CK_DATE, CK_TIMESTAMP, CK_BOOL, CK_F32, CK_DEFAULT, CK_INTERVAL, CK_SYS /* __file_name / __row_index: filled after the parse */ };
+// the shared StrictKind values, plus what only this reader has: CK_TIMESTAMP is a time column with parseTimestampValue in front
+enum CsvKind : int32_t { CK_INT = SK_INT, CK_UINT = SK_UINT, CK_STR = SK_STR, CK_JSONNUM = SK_JSONNUM, CK_DATE = SK_TIME, CK_TIMESTAMP, CK_BOOL = SK_BOOL, CK_F32 = SK_F32, CK_DEFAULT,
+                         CK_INTERVAL = SK_INTERVAL, CK_SYS /* __file_name / __row_index: filled after the parse */ };
+static_assert(CK_TIMESTAMP == 5 && CK_DEFAULT == 8 && CK_SYS == 10, "the tile kernels sort columns by these values");
 
 struct CsvCol {
   int32_t field;      // CSV field index (ColSchema.Path); <0 → DefaultValue
@@ -413,24 +341,17 @@ __device__ __forceinline__ uint32_t spec_lookback(uint32_t *state, int64_t t, ui
   return excl;
 }
 
-__device__ __forceinline__ void store_int(const CsvCol &c, int64_t r, int64_t v) {
-  switch (c.width) {
-    case 1: ((int8_t *)c.values)[r] = (int8_t)v; break;
-    case 2: ((int16_t *)c.values)[r] = (int16_t)v; break;
-    case 4: ((int32_t *)c.values)[r] = (int32_t)v; break;
-    default: ((int64_t *)c.values)[r] = v;
-  }
-}
+// the typed half of a column descriptor, under the StrictKind `kind` (a CK_TIMESTAMP column is SK_TIME to Strictify)
+__device__ __forceinline__ StrictOut strict_out(const CsvCol &c, int32_t kind) { return StrictOut{kind, c.width, c.lo, c.hi, c.values, c.nanos}; }
+__device__ __forceinline__ void store_int(const CsvCol &c, int64_t r, int64_t v) { store_int(strict_out(c, c.kind), r, v); }
 
 // DefaultValue(col) (pkg/abstract/change_item_builders.go:88-109) after Strictify
 __device__ __forceinline__ void store_default(const CsvCol &c, int64_t r) {
   switch (c.kind) {
     case CK_SYS: break;
     case CK_STR: case CK_JSONNUM: c.lens[r] = (c.kind == CK_JSONNUM) ? 1u : 0u; c.fstart[r] = 0x7FFFFFFFu; if (c.kind == CK_JSONNUM) c.fstart[-1] = 1u; break;  // "" / json "0" (a cell that is no byte range: flag word of the column)
-    case CK_DATE: case CK_TIMESTAMP: ((int64_t *)c.values)[r] = 0; if (c.nanos) c.nanos[r] = 0; break;
-    case CK_BOOL: ((uint8_t *)c.values)[r] = 0; break;
-    case CK_F32: ((float *)c.values)[r] = 0.f; break;
-    default: store_int(c, r, 0);
+    case CK_DATE: case CK_TIMESTAMP: store_default(strict_out(c, SK_TIME), r); break;
+    default: store_default(strict_out(c, c.kind), r);
   }
 }
 
@@ -483,26 +404,10 @@ template <class T> __device__ int parsefloat_err(const T &t, uint32_t n) {
 template <class F>
 __device__ int parse_cell(const CsvOpts &o, const CsvCol &c, int64_t r, const F &fv, uint32_t a, uint32_t b, uint32_t npairs, uint64_t abs_start) {
   switch (c.kind) {
-    case CK_INT: case CK_UINT: {
-      // parseNullValues then cast.ToIntNE(string) + range check
+    case CK_INT: case CK_UINT: case CK_INTERVAL:  // parseNullValues, then Strictify
       if (cell_is_null(o, fv, a, b, npairs)) { store_default(c, r); return 0; }
-      if (npairs) return TFGPU_ROW_CAST;  // a '"' survives in the text: not a number
-      uint32_t tb = trim_zero_decimal(fv, a, b);
-      if (c.kind == CK_INT || c.hi != ~0ull) {
-        int64_t v; int rc = parse_int64(fv, a, tb, true, &v);
-        if (rc) return TFGPU_ROW_CAST;
-        if (c.kind == CK_UINT) {
-          if (v < 0) return TFGPU_ROW_CAST;  // errNegativeNotAllowed
-          if ((uint64_t)v > c.hi) return TFGPU_ROW_RANGE;
-        } else if (v < c.lo || v > (int64_t)c.hi) return TFGPU_ROW_RANGE;
-        store_int(c, r, v);
-      } else {  // uint64: cast.ToUint64E parses with ParseUint
-        uint64_t v; int rc = parse_uint64(fv, a, tb, true, &v);
-        if (rc) return TFGPU_ROW_CAST;
-        ((uint64_t *)c.values)[r] = v;
-      }
-      return 0;
-    }
+      if (npairs) return TFGPU_ROW_CAST;  // a '"' survives in the text: not a number, and in a duration an unknown unit
+      return strict_cell(strict_out(c, c.kind), o.cast_tp, o.p128, r, fv, a, b);
     case CK_STR: case CK_JSONNUM: {
       if (c.kind == CK_STR && cell_is_null(o, fv, a, b, npairs)) { c.lens[r] = 0; c.fstart[r] = 0x7FFFFFFFu; return 0; }
       if (c.kind == CK_JSONNUM && o.dp_len && !npairs && b - a >= o.dp_len) {
@@ -534,32 +439,27 @@ __device__ int parse_cell(const CsvOpts &o, const CsvCol &c, int64_t r, const F 
     }
     case CK_DATE: case CK_TIMESTAMP: {
       if (npairs) return TFGPU_ROW_CAST;
-      int64_t sec = 0; int32_t ns = 0; int rc;
-      if (c.kind == CK_TIMESTAMP && parse_int64(fv, a, b, false, &sec) == 0) rc = 0;  // parseTimestampValue :419-426
-      else if (c.kind == CK_DATE && o.user_tp.n && gotime_parse_any(o.user_tp, fv, a, b, &sec, &ns)) rc = 0;  // parseDateValue :405-415
-      else {
-        // still a string: cast.ToTimeE → StringToDate, the first of its layouts that parses (strictify.go:118-143)
-        rc = parse_datetime(fv, a, b, &sec, &ns);
-        if (rc) { ns = 0; rc = gotime_parse_any(o.cast_tp, fv, a, b, &sec, &ns) ? 0 : TFGPU_ROW_CAST; }
+      int64_t sec = 0; int32_t ns = 0;
+      if (c.kind == CK_TIMESTAMP ? parse_int64(fv, a, b, false, &sec) == 0                                // parseTimestampValue :419-426
+                                 : (o.user_tp.n && gotime_parse_any(o.user_tp, fv, a, b, &sec, &ns))) {   // parseDateValue :405-415
+        ((int64_t *)c.values)[r] = sec;
+        c.nanos[r] = ns;
+        return 0;
       }
-      if (rc) return rc;
-      ((int64_t *)c.values)[r] = sec;
-      c.nanos[r] = ns;
-      return 0;
+      return strict_cell(strict_out(c, SK_TIME), o.cast_tp, o.p128, r, fv, a, b);  // still a string
     }
-    case CK_BOOL: {  // parseBooleanValue :431-452 then cast.ToBoolE
-      int v = 0;
+    case CK_BOOL: {  // parseBooleanValue :431-452, then Strictify
+      int v;
       if (npairs) return TFGPU_ROW_CAST;
       if (o.strings_can_be_null && in_list(o, 0, o.n_null, fv, a, b)) v = 0;
       else if (in_list(o, o.n_null, o.n_true, fv, a, b)) v = 1;
       else if (in_list(o, o.n_null + o.n_true, o.n_false, fv, a, b)) v = 0;
-      else if (parse_bool(fv, a, b, &v)) return TFGPU_ROW_CAST;
+      else return strict_cell(strict_out(c, c.kind), o.cast_tp, o.p128, r, fv, a, b);
       ((uint8_t *)c.values)[r] = (uint8_t)v;
       return 0;
     }
-    case CK_F32: {  // parseFloatValue :363-378 (DecimalPoint), then strictify: cast.ToFloat32E(string) = strconv.ParseFloat(s, 32), any error fails the row
+    case CK_F32: {  // parseFloatValue :363-378 (DecimalPoint), then Strictify
       if (npairs) return TFGPU_ROW_CAST;  // a '"' survives in the text: not a number
-      float v = 0; int rc = -1;
       if (o.dp_len && b - a >= o.dp_len) {
         uint32_t k = PATCH_NONE;
         for (uint32_t i = a; i + o.dp_len <= b && k == PATCH_NONE; i++) {
@@ -572,22 +472,10 @@ __device__ int parse_cell(const CsvOpts &o, const CsvCol &c, int64_t r, const F 
           const uint32_t pn = (b - a) - o.dp_len + 1;
           const int pe = parsefloat_err(pt, pn);
           if (pe == 2) return TFGPU_ROW_HOST_FALLBACK;
-          if (pe == 0) rc = parse_float32_go(pt, 0, pn, o.p128, &v);
+          if (pe == 0) return strict_cell(strict_out(c, c.kind), o.cast_tp, o.p128, r, pt, 0, pn);
         }
       }
-      if (rc < 0) rc = parse_float32_go(fv, a, b, o.p128, &v);
-      if (rc == 3) return TFGPU_ROW_HOST_FALLBACK;  // Go's decimal slow path (half-way cases, subnormals, the overflow edge), hex floats, '_'
-      if (rc) return TFGPU_ROW_CAST;                // syntax or range: ToFloat32E returns the error
-      ((float *)c.values)[r] = v;
-      return 0;
-    }
-    case CK_INTERVAL: {  // parseNullValues, then strictify: cast.ToDurationE(string) (strictify.go:142-147)
-      if (cell_is_null(o, fv, a, b, npairs)) { store_default(c, r); return 0; }
-      if (npairs) return TFGPU_ROW_CAST;  // a '"' in the text reads as part of a unit: unknown unit
-      int64_t d;
-      if (parse_duration_go(fv, a, b, &d)) return TFGPU_ROW_CAST;
-      ((int64_t *)c.values)[r] = d;
-      return 0;
+      return strict_cell(strict_out(c, c.kind), o.cast_tp, o.p128, r, fv, a, b);
     }
     default:
       return TFGPU_ROW_HOST_FALLBACK;
@@ -2115,17 +2003,6 @@ __global__ void __launch_bounds__(1024) csv_ml_rows(const uint8_t *fn, const uin
   if (tid == 0) *nrows_out = carry[2];  // complete rows (a row still open at the end of the chunk is not one)
 }
 
-// constructCI's system columns (reader_csv.go:275-290)
-__global__ void csv_fill_row_index(uint64_t *out, int64_t n, uint64_t base) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n) out[r] = base + (uint64_t)r;  // rowsCounter advances for every line read, failed or not (:217-220)
-}
-__global__ void csv_fill_const_text(uint32_t *off, uint8_t *data, int64_t n, const uint8_t *text, uint32_t len) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r > n) return;
-  off[r] = (uint32_t)r * len;
-  if (r < n) for (uint32_t i = 0; i < len; i++) data[(uint64_t)r * len + i] = text[i];
-}
 // csv.Reader.Encoding (reader.go:171-179): every byte through the charmap decoder's table, as UTF-8.  Two passes over
 // 4 KiB tiles: bytes out per tile, then the text.
 static constexpr int ENC_TILE = 4096;
@@ -2469,7 +2346,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   int max_field = -1;
   int si = 0;
   std::vector<int> str_col_index;
-  std::vector<std::pair<int, int>> sys_cols;  // (schema index, 1 = __file_name | 2 = __row_index)
+  std::vector<int> sys_cols;  // schema indices of __file_name / __row_index
   for (int i = 0; i < ncols; i++) {
     const tfgpu_colschema &sc = schema->cols[i];
     CsvCol &c = cols[(size_t)i];
@@ -2480,7 +2357,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
       c.field = -1; c.next = -1; c.kind = CK_SYS;
       DColumn d;
       d.name = cname; d.dtype = sc.dtype; d.repr = sys == 1 ? TFGPU_R_STRING : TFGPU_R_UINT64;
-      sys_cols.push_back({i, sys});
+      sys_cols.push_back(i);
       db->cols.push_back(std::move(d));
       continue;
     }
@@ -2491,25 +2368,10 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     c.field = (int32_t)idx; c.next = -1;
     DColumn d;
     d.name = sc.name ? sc.name : ""; d.dtype = sc.dtype;
-    switch (sc.dtype) {
-      case TFGPU_T_INT8: c.kind = CK_INT; c.width = 1; c.lo = INT8_MIN; c.hi = INT8_MAX; d.repr = TFGPU_R_INT8; break;
-      case TFGPU_T_INT16: c.kind = CK_INT; c.width = 2; c.lo = INT16_MIN; c.hi = INT16_MAX; d.repr = TFGPU_R_INT16; break;
-      case TFGPU_T_INT32: c.kind = CK_INT; c.width = 4; c.lo = INT32_MIN; c.hi = INT32_MAX; d.repr = TFGPU_R_INT32; break;
-      case TFGPU_T_INT64: c.kind = CK_INT; c.width = 8; c.lo = INT64_MIN; c.hi = INT64_MAX; d.repr = TFGPU_R_INT64; break;
-      case TFGPU_T_UINT8: c.kind = CK_UINT; c.width = 1; c.hi = UINT8_MAX; d.repr = TFGPU_R_UINT8; break;
-      case TFGPU_T_UINT16: c.kind = CK_UINT; c.width = 2; c.hi = UINT16_MAX; d.repr = TFGPU_R_UINT16; break;
-      case TFGPU_T_UINT32: c.kind = CK_UINT; c.width = 4; c.hi = UINT32_MAX; d.repr = TFGPU_R_UINT32; break;
-      case TFGPU_T_UINT64: c.kind = CK_UINT; c.width = 8; c.hi = ~0ull; d.repr = TFGPU_R_UINT64; break;
-      case TFGPU_T_BOOLEAN: c.kind = CK_BOOL; c.width = 1; d.repr = TFGPU_R_BOOL; break;
-      case TFGPU_T_DATE: case TFGPU_T_DATETIME: c.kind = CK_DATE; c.width = 8; d.repr = TFGPU_R_TIME; break;
-      case TFGPU_T_TIMESTAMP: c.kind = CK_TIMESTAMP; c.width = 8; d.repr = TFGPU_R_TIME; break;
-      case TFGPU_T_FLOAT32: c.kind = CK_F32; c.width = 4; d.repr = TFGPU_R_FLOAT32; break;
-      case TFGPU_T_FLOAT64: c.kind = CK_JSONNUM; d.repr = TFGPU_R_JSONNUM; break;  // strictify: float64 → json.Number text
-      case TFGPU_T_UTF8: case TFGPU_T_ANY: c.kind = CK_STR; d.repr = TFGPU_R_STRING; break;
-      case TFGPU_T_BYTES: c.kind = CK_STR; d.repr = TFGPU_R_BYTES; break;
-      case TFGPU_T_INTERVAL: c.kind = CK_INTERVAL; c.width = 8; d.repr = TFGPU_R_DURATION; break;
-      default: return tf::fail(TFGPU_ERR_CONFIG, "csv: cannot strictify value of unknown type");
-    }
+    StrictOut so{};
+    d.repr = strict_describe(sc.dtype, so);
+    if (d.repr == TFGPU_R_INVALID) return tf::fail(TFGPU_ERR_CONFIG, "csv: cannot strictify value of unknown type");
+    c.kind = sc.dtype == TFGPU_T_TIMESTAMP ? (int32_t)CK_TIMESTAMP : so.kind; c.width = so.width; c.lo = so.lo; c.hi = so.hi;  // (parseTimestampValue runs in front of a timestamp cell)
     if (c.kind == CK_STR || c.kind == CK_JSONNUM) {
       c.lens = ptr<uint32_t>(lens_all) + (int64_t)si * seg_stride;
       c.fstart = ptr<uint32_t>(fstart_all) + (int64_t)si * fstride + FS_HDR;
@@ -2538,16 +2400,9 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   Buf bcols = up(cols.data(), cols.size() * sizeof(CsvCol)), bff = up(field_first.data(), field_first.size() * 4);
   Buf bloff = up(loff.data(), loff.size() * 4), bldata = up(ldata.data(), ldata.size());
   // time layouts: the user's TimestampParsers, and spf13/cast v1.7.1 StringToDate's list (caste.go timeFormats) in its order
-  static const char *const CAST_LAYOUTS[] = {
-      "2006-01-02", "2006-01-02T15:04:05Z07:00", "2006-01-02T15:04:05", "Mon, 02 Jan 2006 15:04:05 -0700", "Mon, 02 Jan 2006 15:04:05 MST",
-      "02 Jan 06 15:04 -0700", "02 Jan 06 15:04 MST", "Monday, 02-Jan-06 15:04:05 MST", "2006-01-02 15:04:05.999999999 -0700 MST",
-      "2006-01-02T15:04:05-0700", "2006-01-02 15:04:05Z0700", "2006-01-02 15:04:05", "Mon Jan _2 15:04:05 2006", "Mon Jan _2 15:04:05 MST 2006",
-      "Mon Jan 02 15:04:05 -0700 2006", "2006-01-02 15:04:05Z07:00", "02 Jan 2006", "2006-01-02 15:04:05 -07:00", "2006-01-02 15:04:05 -0700",
-      "3:04PM", "Jan _2 15:04:05", "Jan _2 15:04:05.000", "Jan _2 15:04:05.000000", "Jan _2 15:04:05.000000000"};
   std::vector<GtOp> gops; std::string glits; std::vector<uint16_t> gstart_user{0}, gstart_cast;
   for (int i = 0; i < opts->n_timestamp_parsers; i++) { gotime_compile(opts->timestamp_parsers[i] ? opts->timestamp_parsers[i] : "", gops, glits); gstart_user.push_back((uint16_t)gops.size()); }
-  gstart_cast.push_back((uint16_t)gops.size());
-  for (const char *l : CAST_LAYOUTS) { gotime_compile(l, gops, glits); gstart_cast.push_back((uint16_t)gops.size()); }
+  append_cast_layouts(gops, glits, gstart_cast);
   Buf bgops = up(gops.data(), gops.size() * sizeof(GtOp)), bglits = up(glits.data(), glits.size());
   Buf bgsu = up(gstart_user.data(), gstart_user.size() * 2), bgsc = up(gstart_cast.data(), gstart_cast.size() * 2), bdp = up(dp.data(), dp.size());
   Buf patch_all;
@@ -2583,7 +2438,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   pp.o.n_null = opts->n_null_values; pp.o.n_true = opts->n_true_values; pp.o.n_false = opts->n_false_values;
   pp.o.list_off = ptr<uint32_t>(bloff); pp.o.list_data = ptr<uint8_t>(bldata);
   pp.o.user_tp = GtSet{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgsu), opts->n_timestamp_parsers};
-  pp.o.cast_tp = GtSet{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgsc), (int32_t)(sizeof CAST_LAYOUTS / sizeof *CAST_LAYOUTS)};
+  pp.o.cast_tp = GtSet{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgsc), N_CAST_LAYOUTS};
   pp.o.dp = ptr<uint8_t>(bdp); pp.o.dp_len = (uint32_t)dp.size(); pp.o.multiline = multiline ? 1u : 0u;
   pp.o.p128 = nullptr;
   for (auto &c : cols) if (c.kind == CK_F32) pp.o.p128 = reinterpret_cast<const uint64_t *>(pow10_table() + 632);
@@ -2811,25 +2666,10 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     materialize_from(*db, data);
   }
 
-  for (auto &sy : sys_cols) {  // constructCI :275-290
-    DColumn &d = db->cols[(size_t)sy.first];
-    const int64_t n1 = std::max<int64_t>(nrows, 1);
-    if (sy.second == 2) {
-      d.values = dalloc((size_t)n1 * 8);
-      if (nrows) csv_fill_row_index<<<blocks_for(nrows, 256), 256, 0, st>>>(ptr<uint64_t>(d.values), nrows, opts->row_number_base);
-    } else {
-      const std::string fn = opts->file_name ? opts->file_name : "";
-      Buf btext = upload_small(fn.data(), fn.size());
-      d.offsets = dalloc((size_t)(nrows + 1) * 4 + 16);
-      d.data_len = (uint64_t)fn.size() * (uint64_t)nrows;
-      if (d.data_len >> 32) return tf::fail(TFGPU_ERR_UNSUPPORTED, "csv: __file_name column exceeds 4 GiB");
-      d.data = dalloc(d.data_len + 8);
-      csv_fill_const_text<<<blocks_for(nrows + 1, 256), 256, 0, st>>>(ptr<uint32_t>(d.offsets), ptr<uint8_t>(d.data), nrows, ptr<uint8_t>(btext), (uint32_t)fn.size());
-    }
-    if (opts->hide_system_cols) {  // config.hideSystemCols: both are nil
-      d.validity = dalloc_zero((size_t)(nrows + 7) / 8 + 8);
-      if (sy.second == 1) { d.data_len = 0; TF_HIP(hipMemsetAsync(d.offsets->p, 0, (size_t)(nrows + 1) * 4, st)); }
-    }
+  for (int i : sys_cols) {  // constructCI :275-290; rowsCounter advances for every line read, failed or not (:217-220)
+    std::string detail;
+    const int rc = fill_system_column(db->cols[(size_t)i], nrows, opts->file_name, opts->row_number_base, nullptr, opts->hide_system_cols, &detail);
+    if (rc) return tf::fail(rc, "csv: " + detail);
   }
 
   std::unique_ptr<tfgpu_dbatch> result;
@@ -2867,269 +2707,4 @@ extern "C" int tfgpu_csv_parse(const tfgpu_csv_options *opts, const tfgpu_schema
   int rc = csv_parse_body(opts, schema, bytes, len, mem, out, consumed, errs, errs_cap, nerrs, true, &retry);
   if (rc == TFGPU_OK && retry) { retry = false; rc = csv_parse_body(opts, schema, bytes, len, mem, out, consumed, errs, errs_cap, nerrs, false, &retry); }
   return rc;
-}
-
-// ======================================================================================================
-// tfgpu_strictify — strictify.Strictify (pkg/abstract/changeitem/strictify/strictify.go:17-157) over a device batch: what the
-// strictifying serializers run before they serialize (pkg/serializer/strictify.go:24-36).  Every column named by the
-// TableSchema is brought to the strict Go type of its DataType.  The text → typed conversions ARE the CSV ingest's cell
-// conversions (parse_cell with reader options that do nothing); the integer family converts with Go's range rules.
-// ======================================================================================================
-namespace tf {
-
-enum StrictMode : int32_t { SM_TEXT = 1, SM_TEXT_JSONNUM_OUT = 2, SM_INTS = 3, SM_JSONNUM_TO_TIME = 4, SM_FAIL = 5 /* no conversion exists: every value fails */,
-                            SM_FLOATS = 6 /* Go float64 / float32 values under integer / bool / float DataTypes */ };
-DColumn column_to_text(const DColumn &c, int64_t n, bool to_bytes);  // tf_transform.hip: fmt's %v of integers, bools, time.Time, time.Duration = their strconv / String() forms
-struct StrictCol {
-  int32_t mode, src_repr;
-  const void *values; const uint32_t *offsets; const uint8_t *data; const uint8_t *validity;
-  CsvCol out;
-};
-__device__ __forceinline__ bool strict_load_int(const StrictCol &c, int64_t r, int64_t *v, uint64_t *u, bool *is_unsigned) {
-  *is_unsigned = false;
-  switch (c.src_repr) {
-    case TFGPU_R_INT8: *v = ((const int8_t *)c.values)[r]; return true;
-    case TFGPU_R_INT16: *v = ((const int16_t *)c.values)[r]; return true;
-    case TFGPU_R_INT32: *v = ((const int32_t *)c.values)[r]; return true;
-    case TFGPU_R_INT64: *v = ((const int64_t *)c.values)[r]; return true;
-    case TFGPU_R_UINT8: case TFGPU_R_BOOL: *u = ((const uint8_t *)c.values)[r]; break;
-    case TFGPU_R_UINT16: *u = ((const uint16_t *)c.values)[r]; break;
-    case TFGPU_R_UINT32: *u = ((const uint32_t *)c.values)[r]; break;
-    case TFGPU_R_UINT64: *u = ((const uint64_t *)c.values)[r]; break;
-    default: return false;
-  }
-  *is_unsigned = true; *v = (int64_t)*u;
-  return true;
-}
-// item = column * nrows + row; first_bad[column] = min over failing rows of (row << 8 | tfgpu_rowerr)
-__global__ void __launch_bounds__(256) strictify_cells(CsvOpts o, const StrictCol *cols, int32_t ncols, int64_t nrows, unsigned long long *first_bad) {
-  const int32_t j = (int32_t)blockIdx.y; const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (the column is the grid's y: a scalar)
-  if (r >= nrows || j >= ncols) return;
-  const StrictCol &c = cols[j];
-  if (c.validity && !((c.validity[r >> 3] >> (r & 7)) & 1)) { if (c.mode != SM_TEXT_JSONNUM_OUT && c.mode != SM_FAIL) store_default(c.out, r); return; }  // nil stays nil
-  int rc = 0;
-  if (c.mode == SM_FAIL) rc = TFGPU_ROW_CAST;  // castx.ToByteSliceE of anything but []byte / string: "no known conversion"
-  else if (c.mode == SM_FLOATS) {
-    // cast.ToInt64E / ToUint64E / ToBoolE / ToFloat32E of a float: Go conversions (caste.go of spf13/cast); what a conversion of a NaN or of a
-    // magnitude beyond the integer range yields is the machine's business, so those go back to the host
-    const double f = c.src_repr == TFGPU_R_FLOAT32 ? (double)((const float *)c.values)[r] : ((const double *)c.values)[r];
-    switch (c.out.kind) {
-      case CK_INT:
-        if (!(f > -9223372036854775808.0 && f < 9223372036854775808.0)) rc = TFGPU_ROW_HOST_FALLBACK;
-        else { const int64_t x = (int64_t)f; if (x < c.out.lo || x > (int64_t)c.out.hi) rc = TFGPU_ROW_RANGE; else store_int(c.out, r, x); }
-        break;
-      case CK_UINT:
-        if (f != f || f >= 18446744073709551616.0) rc = TFGPU_ROW_HOST_FALLBACK;
-        else if (f < 0) rc = TFGPU_ROW_CAST;  // errNegativeNotAllowed
-        else { const uint64_t x = (uint64_t)f; if (x > c.out.hi) rc = TFGPU_ROW_RANGE; else if (c.out.width == 8) ((uint64_t *)c.out.values)[r] = x; else store_int(c.out, r, (int64_t)x); }
-        break;
-      case CK_BOOL: ((uint8_t *)c.out.values)[r] = f != 0 ? 1 : 0; break;
-      default: ((float *)c.out.values)[r] = (float)f;  // CK_F32
-    }
-  }
-  else if (c.mode == SM_INTS) {
-    int64_t v = 0; uint64_t u = 0; bool uns = false;
-    strict_load_int(c, r, &v, &u, &uns);
-    switch (c.out.kind) {
-      case CK_INT:  // cast.ToInt64E of an integer kind is a Go conversion (a uint64 wraps), then toSignedInt's limits (strictify.go:159-169)
-        if (v < c.out.lo || v > (int64_t)c.out.hi) rc = TFGPU_ROW_RANGE; else store_int(c.out, r, v);
-        break;
-      case CK_UINT:  // errNegativeNotAllowed, then toUnsignedInt's limit (:171-181)
-        if (!uns && v < 0) rc = TFGPU_ROW_CAST;
-        else { const uint64_t x = uns ? u : (uint64_t)v; if (x > c.out.hi) rc = TFGPU_ROW_RANGE; else if (c.out.width == 8) ((uint64_t *)c.out.values)[r] = x; else store_int(c.out, r, (int64_t)x); }
-        break;
-      case CK_BOOL: ((uint8_t *)c.out.values)[r] = (uns ? u != 0 : v != 0) ? 1 : 0; break;
-      case CK_F32: ((float *)c.out.values)[r] = uns ? (float)(double)u : (float)(double)v; break;
-      case CK_DATE: case CK_TIMESTAMP: ((int64_t *)c.out.values)[r] = v; c.out.nanos[r] = 0; break;
-      default: ((int64_t *)c.out.values)[r] = v;  // CK_INTERVAL: time.Duration(v)
-    }
-  } else {
-    const uint32_t a = c.offsets[r], n = c.offsets[r + 1] - a;
-    MemBytes rd(c.data);
-    const Field fv{&rd, a, n};
-    if (c.mode == SM_TEXT_JSONNUM_OUT) rc = json_number_ok(fv, 0, n) ? 0 : TFGPU_ROW_CAST;  // castx.ToJSONNumberE: the text itself is the json.Number
-    else if (c.mode == SM_JSONNUM_TO_TIME) {  // cast.ToTimeE(json.Number): its Int64 as Unix seconds
-      int64_t sec;
-      if (parse_int64(fv, 0, n, false, &sec)) rc = TFGPU_ROW_CAST; else { ((int64_t *)c.out.values)[r] = sec; c.out.nanos[r] = 0; }
-    } else rc = parse_cell(o, c.out, r, fv, 0, n, 0, 0);
-  }
-  if (rc) atomicMin(&first_bad[j], ((unsigned long long)r << 8) | (unsigned long long)rc);
-}
-
-// castx.ToStringE of a Go float (caste.go:64-67): strconv.FormatFloat(f, 'f', -1, bits) — the text of a "utf8" column, and (through
-// castx.ToJSONNumberE) the json.Number of a "double" one
-__global__ void __launch_bounds__(256) strict_float_text(const void *values, int is32, const uint8_t *validity, int64_t n, uint32_t *off, uint8_t *data) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const bool nil = validity && !((validity[r >> 3] >> (r & 7)) & 1);
-  const double f = is32 ? (double)((const float *)values)[r] : ((const double *)values)[r];
-  if (!data) { dev::CountOut c; if (!nil) dev::fmt_float(c, f, 'f', is32 ? 32 : 64); off[r] = c.n; return; }
-  if (nil) return;
-  dev::StoreOut o{data + off[r]};
-  dev::fmt_float(o, f, 'f', is32 ? 32 : 64);
-}
-static DColumn float_column_text(const DColumn &c, int64_t n) {
-  hipStream_t st = ctx().stream;
-  DColumn o;
-  o.offsets = dalloc((size_t)(n + 1) * 4 + 16);
-  const int is32 = c.repr == TFGPU_R_FLOAT32;
-  if (n) strict_float_text<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(c.values->p, is32, ptr<uint8_t>(c.validity), n, ptr<uint32_t>(o.offsets), nullptr);
-  exclusive_scan_u32(ptr<uint32_t>(o.offsets), ptr<uint32_t>(o.offsets), n, true);
-  const uint32_t *tot = d2h_u32(ptr<uint32_t>(o.offsets) + n);
-  tf::sync();
-  o.data_len = *tot;
-  o.data = dalloc((size_t)o.data_len + 16);
-  if (n) strict_float_text<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(c.values->p, is32, ptr<uint8_t>(c.validity), n, ptr<uint32_t>(o.offsets), ptr<uint8_t>(o.data));
-  o.validity = c.validity;
-  return o;
-}
-
-}  // namespace tf
-
-extern "C" int tfgpu_strictify(const tfgpu_dbatch *in, const tfgpu_schema *schema, tfgpu_dbatch **out, int64_t *bad_row, int32_t *bad_col) {
-  TF_API_BEGIN
-  tf::dense(in);  // its rows may still be a selection (tfgpu_dbatch::pending)
-  if (!in || !out) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_strictify: null argument");
-  Context &cx = ctx();
-  std::lock_guard<std::mutex> lk(cx.mu);
-  hipStream_t st = cx.stream;
-  materialize(*in);
-  const int64_t n = in->nrows;
-  if (bad_row) *bad_row = -1;
-  if (bad_col) *bad_col = -1;
-  auto dtype_of = [&](const DColumn &c) -> int {  // tableSchema[columnName]; a column the schema does not name is left alone
-    if (schema) { for (int i = 0; i < schema->ncols; i++) if (schema->cols[i].name && c.name == schema->cols[i].name) return schema->cols[i].dtype; return -1; }
-    if (!in->schema.empty()) { for (auto &p : in->schema) if (p.first == c.name) return p.second; return -1; }
-    return c.dtype;
-  };
-  auto r = std::make_unique<tfgpu_dbatch>(*in);  // shares every buffer; converted columns are replaced below
-  std::vector<StrictCol> sc; std::vector<int> which;
-  std::vector<size_t> float_text;  // Go floats under "utf8" / "double": FormatFloat 'f'
-  std::vector<size_t> to_text;  // columns whose strict form is their text (castx.ToStringE of a number / bool / time): made after the checks, they cannot fail
-  bool need_p128 = false;
-  for (size_t i = 0; i < in->cols.size(); i++) {
-    const DColumn &c = in->cols[i];
-    const int dt = dtype_of(c);
-    if (dt < 0 || dt == TFGPU_T_ANY) continue;
-    DColumn &d = r->cols[i];
-    d.dtype = dt;
-    CsvCol oc{}; int strict = TFGPU_R_INVALID;
-    switch (dt) {
-      case TFGPU_T_INT8: oc.kind = CK_INT; oc.width = 1; oc.lo = INT8_MIN; oc.hi = INT8_MAX; strict = TFGPU_R_INT8; break;
-      case TFGPU_T_INT16: oc.kind = CK_INT; oc.width = 2; oc.lo = INT16_MIN; oc.hi = INT16_MAX; strict = TFGPU_R_INT16; break;
-      case TFGPU_T_INT32: oc.kind = CK_INT; oc.width = 4; oc.lo = INT32_MIN; oc.hi = INT32_MAX; strict = TFGPU_R_INT32; break;
-      case TFGPU_T_INT64: oc.kind = CK_INT; oc.width = 8; oc.lo = INT64_MIN; oc.hi = INT64_MAX; strict = TFGPU_R_INT64; break;
-      case TFGPU_T_UINT8: oc.kind = CK_UINT; oc.width = 1; oc.hi = UINT8_MAX; strict = TFGPU_R_UINT8; break;
-      case TFGPU_T_UINT16: oc.kind = CK_UINT; oc.width = 2; oc.hi = UINT16_MAX; strict = TFGPU_R_UINT16; break;
-      case TFGPU_T_UINT32: oc.kind = CK_UINT; oc.width = 4; oc.hi = UINT32_MAX; strict = TFGPU_R_UINT32; break;
-      case TFGPU_T_UINT64: oc.kind = CK_UINT; oc.width = 8; oc.hi = ~0ull; strict = TFGPU_R_UINT64; break;
-      case TFGPU_T_BOOLEAN: oc.kind = CK_BOOL; oc.width = 1; strict = TFGPU_R_BOOL; break;
-      case TFGPU_T_DATE: case TFGPU_T_DATETIME: case TFGPU_T_TIMESTAMP: oc.kind = CK_DATE; oc.width = 8; strict = TFGPU_R_TIME; break;  // cast.ToTimeE: StringToDate only (no reader step)
-      case TFGPU_T_FLOAT32: oc.kind = CK_F32; oc.width = 4; strict = TFGPU_R_FLOAT32; break;
-      case TFGPU_T_FLOAT64: oc.kind = CK_JSONNUM; strict = TFGPU_R_JSONNUM; break;
-      case TFGPU_T_UTF8: oc.kind = CK_STR; strict = TFGPU_R_STRING; break;
-      case TFGPU_T_BYTES: oc.kind = CK_STR; strict = TFGPU_R_BYTES; break;
-      case TFGPU_T_INTERVAL: oc.kind = CK_INTERVAL; oc.width = 8; strict = TFGPU_R_DURATION; break;
-      default: return tf::fail(TFGPU_ERR_CONFIG, "tfgpu_strictify: cannot strictify value of unknown type (column " + c.name + ")");
-    }
-    if (c.repr == strict) continue;  // already the strict Go type
-    const bool text = c.repr == TFGPU_R_STRING || c.repr == TFGPU_R_JSONNUM;
-    const bool ints = (c.repr >= TFGPU_R_INT8 && c.repr <= TFGPU_R_UINT64) || c.repr == TFGPU_R_BOOL;
-    auto unsupported = [&]() { return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_strictify: column " + c.name + ": a " + std::string(type_name(dt)) + " column holding Go values of representation " + std::to_string(c.repr) + " is converted on the host (cast." "To…E of that kind is not device-resident)"); };
-    StrictCol s{};
-    s.src_repr = c.repr; s.values = c.values ? c.values->p : nullptr; s.offsets = ptr<uint32_t>(c.offsets); s.data = ptr<uint8_t>(c.payload()); s.validity = ptr<uint8_t>(c.validity);
-    if (text && (oc.kind == CK_STR)) {  // castx.ToStringE / ToByteSliceE of a string (or of a json.Number's text): the same bytes
-      if (c.repr == TFGPU_R_JSONNUM && dt == TFGPU_T_BYTES) return unsupported();
-      d.repr = strict;
-      continue;
-    }
-    if (c.repr == TFGPU_R_BYTES && dt == TFGPU_T_UTF8) { d.repr = TFGPU_R_STRING; continue; }  // ToStringE([]byte) = string(b)
-    if (text && oc.kind == CK_JSONNUM) { if (c.repr != TFGPU_R_STRING) continue; s.mode = SM_TEXT_JSONNUM_OUT; d.repr = TFGPU_R_JSONNUM; }
-    else if (text) {
-      if (c.repr == TFGPU_R_JSONNUM && oc.kind == CK_INTERVAL) return unsupported();
-      s.mode = (c.repr == TFGPU_R_JSONNUM && oc.kind == CK_DATE) ? SM_JSONNUM_TO_TIME : SM_TEXT;
-      if (oc.kind == CK_F32) need_p128 = true;
-    } else if ((ints || c.repr == TFGPU_R_TIME || c.repr == TFGPU_R_DURATION) && dt == TFGPU_T_UTF8) {
-      to_text.push_back(i);  // castx.ToStringE (caste.go:58-106): FormatInt / FormatUint / FormatBool, Time.String(), Duration.String()
-      continue;
-    } else if ((ints || c.repr == TFGPU_R_TIME || c.repr == TFGPU_R_DURATION || c.repr == TFGPU_R_FLOAT32 || c.repr == TFGPU_R_FLOAT64) && dt == TFGPU_T_BYTES) {
-      s.mode = SM_FAIL;        // castx.ToByteSliceE (caste.go:16-28) takes []byte and string only: the first value fails the call
-    } else if ((c.repr == TFGPU_R_FLOAT32 || c.repr == TFGPU_R_FLOAT64) && (dt == TFGPU_T_UTF8 || dt == TFGPU_T_FLOAT64)) {
-      float_text.push_back(i);  // FormatFloat(f, 'f', -1, bits): the string, or — every such text parses (fastfloat takes "NaN" and "+Inf" too) — the json.Number
-      continue;
-    } else if ((c.repr == TFGPU_R_FLOAT32 || c.repr == TFGPU_R_FLOAT64) && (oc.kind == CK_INT || oc.kind == CK_UINT || oc.kind == CK_BOOL || oc.kind == CK_F32)) {
-      s.mode = SM_FLOATS;
-    } else if (ints) {
-      if (oc.kind == CK_STR || oc.kind == CK_JSONNUM) return unsupported();                 // an integer under "double": castx.ToJSONNumberE of its text — host
-      if (oc.kind == CK_INTERVAL && (c.repr >= TFGPU_R_UINT8 && c.repr <= TFGPU_R_UINT64)) return unsupported();
-      if (c.repr == TFGPU_R_BOOL && (oc.kind == CK_DATE || oc.kind == CK_INTERVAL || oc.kind == CK_F32)) return unsupported();
-      s.mode = SM_INTS;
-    } else return unsupported();
-    if (s.mode == SM_FAIL) {  // reached only when every row is nil: an all-nil []byte column
-      d.values = nullptr; d.nanos = nullptr; d.view = nullptr; d.data_len = 0;
-      d.offsets = dalloc_zero((size_t)(n + 1) * 4 + 16); d.data = dalloc(16);
-      d.repr = strict;
-    } else if (s.mode != SM_TEXT_JSONNUM_OUT) {
-      d.values = dalloc((size_t)std::max<int64_t>(n, 1) * (size_t)oc.width);
-      d.offsets = nullptr; d.data = nullptr; d.view = nullptr; d.data_len = 0; d.nanos = nullptr;
-      if (oc.kind == CK_DATE) d.nanos = dalloc((size_t)std::max<int64_t>(n, 1) * 4);
-      d.repr = strict;
-      oc.values = d.values->p; oc.nanos = ptr<int32_t>(d.nanos);
-    }
-    s.out = oc;
-    sc.push_back(s); which.push_back((int)i);
-  }
-  if (!sc.empty() && n > 0) {
-    // neutral reader options: no null / true / false lists, no DecimalPoint, no user layouts — what is left of parse_cell is strictifyValue
-    static const char *const CAST_LAYOUTS[] = {
-        "2006-01-02", "2006-01-02T15:04:05Z07:00", "2006-01-02T15:04:05", "Mon, 02 Jan 2006 15:04:05 -0700", "Mon, 02 Jan 2006 15:04:05 MST",
-        "02 Jan 06 15:04 -0700", "02 Jan 06 15:04 MST", "Monday, 02-Jan-06 15:04:05 MST", "2006-01-02 15:04:05.999999999 -0700 MST",
-        "2006-01-02T15:04:05-0700", "2006-01-02 15:04:05Z0700", "2006-01-02 15:04:05", "Mon Jan _2 15:04:05 2006", "Mon Jan _2 15:04:05 MST 2006",
-        "Mon Jan 02 15:04:05 -0700 2006", "2006-01-02 15:04:05Z07:00", "02 Jan 2006", "2006-01-02 15:04:05 -07:00", "2006-01-02 15:04:05 -0700",
-        "3:04PM", "Jan _2 15:04:05", "Jan _2 15:04:05.000", "Jan _2 15:04:05.000000", "Jan _2 15:04:05.000000000"};
-    std::vector<GtOp> gops; std::string glits; std::vector<uint16_t> gstart{0};
-    for (const char *l : CAST_LAYOUTS) { gotime_compile(l, gops, glits); gstart.push_back((uint16_t)gops.size()); }
-    Buf bgops = upload_const(gops.data(), gops.size() * sizeof(GtOp)), bglits = upload_const(glits.data(), glits.size()), bgs = upload_const(gstart.data(), gstart.size() * 2);
-    CsvOpts o{};
-    o.delim = ','; o.quote = '"';
-    o.user_tp = GtSet{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgs), 0};
-    o.cast_tp = GtSet{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgs), (int32_t)(sizeof CAST_LAYOUTS / sizeof *CAST_LAYOUTS)};
-    o.p128 = need_p128 ? reinterpret_cast<const uint64_t *>(pow10_table() + 632) : nullptr;
-    Buf bsc = upload_small(sc.data(), sc.size() * sizeof(StrictCol));
-    Buf bad = dalloc(sc.size() * 8);
-    TF_HIP(hipMemsetAsync(bad->p, 0xFF, sc.size() * 8, st));
-    {
-      KernelTimer t("strictify_cells");
-      strictify_cells<<<dim3((unsigned)((n + 255) / 256), (unsigned)sc.size()), 256, 0, st>>>(o, reinterpret_cast<const StrictCol *>(bsc->p), (int32_t)sc.size(), n, reinterpret_cast<unsigned long long *>(bad->p));
-    }
-    std::vector<uint64_t> hb(sc.size());
-    d2h(hb.data(), bad->p, hb.size() * 8);
-    tf::sync();
-    // the first failing value in the reference's order: rows in order, a row's columns in order
-    uint64_t best = ~0ull; int bcol = -1;
-    for (size_t k = 0; k < hb.size(); k++) if (hb[k] != ~0ull && ((hb[k] >> 8) < (best >> 8) || best == ~0ull)) { best = hb[k]; bcol = which[k]; }
-    if (bcol >= 0) {
-      const int64_t row = (int64_t)(best >> 8); const int code = (int)(best & 0xFF);
-      if (bad_row) *bad_row = row;
-      if (bad_col) *bad_col = bcol;
-      if (code == TFGPU_ROW_HOST_FALLBACK)
-        return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_strictify: row " + std::to_string(row) + ", column " + in->cols[(size_t)bcol].name + ": a value form the device does not decide (Go's decimal slow path, a free-form date): strictify this batch on the host");
-      return tf::fail(TFGPU_ERR_INVALID, "failed to strictify the value of column [" + std::to_string(bcol) + "] \"" + in->cols[(size_t)bcol].name + "\": row " + std::to_string(row) + ": " + (code == TFGPU_ROW_RANGE ? "value is out of the type's range" : "unable to cast the value"));
-    }
-  }
-  for (size_t i : float_text) {
-    const int dt = r->cols[i].dtype;
-    DColumn t = float_column_text(in->cols[i], n);
-    t.name = in->cols[i].name; t.dtype = dt; t.repr = dt == TFGPU_T_FLOAT64 ? TFGPU_R_JSONNUM : TFGPU_R_STRING;
-    r->cols[i] = std::move(t);
-  }
-  for (size_t i : to_text) {
-    const int dt = r->cols[i].dtype;
-    DColumn t = column_to_text(in->cols[i], n, false);
-    t.name = in->cols[i].name; t.dtype = dt;
-    r->cols[i] = std::move(t);
-  }
-  *out = r.release();
-  return TFGPU_OK;
-  TF_API_END
 }

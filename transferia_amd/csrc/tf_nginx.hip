@@ -2,9 +2,7 @@
 // compiler and the schema resolver (host, no GPU), and the device front of tfgpu_nginx_parse: which lines are blank, every other
 // line's lineCounter, the token walk (parseEntry) — one lane per line, the lines staged in LDS by the whole wave — and the cells:
 // convertNginxValue, constructCI and strictify.Strictify over the cut fields, the system columns, the compaction, the error list.
-// The text -> typed conversions are the ones parse_cell (tf_csv.hip) runs for tfgpu_strictify, built here from the same shared
-// parsers (tf_devparse.hpp, tf_gotime.hpp, tf_f64range.hpp): tf_csv.hip is pinned by the PMC evidence of profiles/pmc_traffic.json
-// (a stamp of its bytes) and is left as it is; folding both onto one parse_cell in a header belongs with the next evidence visit.
+// The text -> typed conversion is strict_cell (tf_strictcell.hpp), the one the CSV ingest and tfgpu_strictify run.
 #include <algorithm>
 #include <map>
 
@@ -14,6 +12,7 @@
 #include "tf_devfloat.hpp"
 #include "tf_f64range.hpp"
 #include "tf_gotime.hpp"
+#include "tf_strictcell.hpp"
 #include "tf_textview.hpp"
 
 using namespace tf;
@@ -370,117 +369,22 @@ __global__ void __launch_bounds__(NG_LINES) nginx_parse_lines(NgParams p) {
 
 
 // ---- cells: convertNginxValue, constructCI (reader_nginx_funcs.go:32-47, reader_nginx.go:217-279), strictify.Strictify --------
-enum NgKind : int32_t { NK_INT, NK_UINT, NK_STR, NK_JSONNUM, NK_TIME, NK_BOOL, NK_F32, NK_INTERVAL };
 enum NgMode : int32_t { NGM_STRICT = 0 /* the string through Strictify */, NGM_LAYOUT = 1 /* date / datetime: time.Parse(timeLocalLayout) */,
                         NGM_DEFAULT = 2 /* the index is outside the fields: abstract.DefaultValue */ };
 struct NgCol {
-  int32_t kind, width, slot, mode;
+  StrictOut out;               // kind, width, limits, values, nanos
+  int32_t slot, mode;
   int32_t schema_col, pad;     // the column's index in the schema: what a row error names
-  int64_t lo; uint64_t hi;     // toSignedInt / toUnsignedInt limits (strictify.go:159-181)
-  void *values; int32_t *nanos;
   uint32_t *lens, *fstart;     // text: content length (Arrow offsets after the scan) and where the cell sits in the chunk (tf_textview.hpp)
   unsigned long long *valid;   // bit r = the cell is not nil
 };
 
-__device__ __forceinline__ void ng_store_int(const NgCol &c, int64_t r, int64_t v) {
-  switch (c.width) {
-    case 1: ((int8_t *)c.values)[r] = (int8_t)v; break;
-    case 2: ((int16_t *)c.values)[r] = (int16_t)v; break;
-    case 4: ((int32_t *)c.values)[r] = (int32_t)v; break;
-    default: ((int64_t *)c.values)[r] = v;
-  }
-}
 // abstract.DefaultValue (change_item_builders.go:88-109) after Strictify; also what a nil cell's slot holds
 __device__ __forceinline__ void ng_store_default(const NgCol &c, int64_t r, bool nil) {
-  switch (c.kind) {
-    case NK_STR: c.lens[r] = 0; c.fstart[r] = nil ? 0u : 0x7FFFFFFFu; break;
-    case NK_JSONNUM: c.lens[r] = nil ? 0u : 1u; c.fstart[r] = nil ? 0u : 0x7FFFFFFFu; break;  // float64(0) is json.Number("0"): a cell that is no byte range
-    case NK_TIME: ((int64_t *)c.values)[r] = 0; c.nanos[r] = 0; break;
-    case NK_BOOL: ((uint8_t *)c.values)[r] = 0; break;
-    case NK_F32: ((float *)c.values)[r] = 0.f; break;
-    default: ng_store_int(c, r, 0);
-  }
-}
-// spf13/cast trimZeroDecimal: "12.00" -> "12"
-template <class F> __device__ __forceinline__ uint32_t ng_trim_zero_decimal(const F &f, uint32_t a, uint32_t b) {
-  bool found_zero = false;
-  for (uint32_t i = b; i > a; i--) {
-    const uint32_t c = f[i - 1];
-    if (c == '.') { if (found_zero) return i - 1; }
-    else if (c == '0') found_zero = true;
-    else return b;
-  }
-  return b;
-}
-// castx.ToJSONNumberE's acceptance: fastfloat.Parse's grammar, or inf / infinity / nan in any case
-template <class F> __device__ bool ng_json_number_ok(const F &f, uint32_t a, uint32_t b) {
-  if (a >= b) return false;
-  uint32_t p = a;
-  if (f[p] == '-' || f[p] == '+') p++;
-  const uint32_t d0 = p;
-  while (p < b && dg(f[p])) p++;
-  uint32_t nd = p - d0; bool ok = true;
-  if (p < b && f[p] == '.') { p++; const uint32_t f0 = p; while (p < b && dg(f[p])) p++; if (p == f0) nd = 0; else nd += p - f0; }
-  if (nd > 0 && p < b && (f[p] == 'e' || f[p] == 'E')) { p++; if (p < b && (f[p] == '-' || f[p] == '+')) p++; const uint32_t x0 = p; while (p < b && dg(f[p])) p++; if (p == x0) ok = false; }
-  if (ok && nd > 0 && p == b) return true;
-  uint32_t q = a;
-  if (f[q] == '-' || f[q] == '+') q++;
-  const uint32_t n = b - q;
-  auto ci = [&](const char *s, uint32_t sl) { if (n != sl) return false; for (uint32_t i = 0; i < sl; i++) if (lower_(f[q + i]) != (uint32_t)s[i]) return false; return true; };
-  return ci("inf", 3) || ci("infinity", 8) || ci("nan", 3);
-}
-// strictifyValue of the string fv[0, n) under column c (strictify.go:75-157): cast.ToInt64E / ToUint64E + range, castx.ToJSONNumberE,
-// cast.ToTimeE (StringToDate: the first of its layouts that parses), cast.ToBoolE, ToFloat32E, ToDurationE; text stays where it is.
-// Returns tfgpu_rowerr.
-template <class F> __device__ int ng_strict_cell(const NgCol &c, const GtSet &cast_tp, const uint64_t *p128, int64_t r, const F &fv, uint32_t n, uint32_t abs_start) {
-  switch (c.kind) {
-    case NK_INT: case NK_UINT: {
-      const uint32_t tb = ng_trim_zero_decimal(fv, 0, n);
-      if (c.kind == NK_INT || c.hi != ~0ull) {
-        int64_t v;
-        if (parse_int64(fv, 0, tb, true, &v)) return TFGPU_ROW_CAST;
-        if (c.kind == NK_UINT) {
-          if (v < 0) return TFGPU_ROW_CAST;  // errNegativeNotAllowed
-          if ((uint64_t)v > c.hi) return TFGPU_ROW_RANGE;
-        } else if (v < c.lo || v > (int64_t)c.hi) return TFGPU_ROW_RANGE;
-        ng_store_int(c, r, v);
-      } else {  // uint64: cast.ToUint64E parses with ParseUint
-        uint64_t v;
-        if (parse_uint64(fv, 0, tb, true, &v)) return TFGPU_ROW_CAST;
-        ((uint64_t *)c.values)[r] = v;
-      }
-      return 0;
-    }
-    case NK_STR: case NK_JSONNUM:
-      if (c.kind == NK_JSONNUM && !ng_json_number_ok(fv, 0, n)) return TFGPU_ROW_CAST;
-      c.lens[r] = n; c.fstart[r] = abs_start;
-      return 0;
-    case NK_TIME: {
-      int64_t sec = 0; int32_t ns = 0;
-      if (!gotime_parse_any(cast_tp, fv, 0, n, &sec, &ns)) return TFGPU_ROW_CAST;
-      ((int64_t *)c.values)[r] = sec; c.nanos[r] = ns;
-      return 0;
-    }
-    case NK_BOOL: {
-      int v = 0;
-      if (parse_bool(fv, 0, n, &v)) return TFGPU_ROW_CAST;
-      ((uint8_t *)c.values)[r] = (uint8_t)v;
-      return 0;
-    }
-    case NK_F32: {
-      float v = 0;
-      const int rc = parse_float32_go(fv, 0, n, p128, &v);
-      if (rc == 3) return TFGPU_ROW_HOST_FALLBACK;  // Go's decimal slow path (half-way cases, subnormals, the overflow edge), hex floats, '_'
-      if (rc) return TFGPU_ROW_CAST;
-      ((float *)c.values)[r] = v;
-      return 0;
-    }
-    default: {  // NK_INTERVAL
-      int64_t d;
-      if (parse_duration_go(fv, 0, n, &d)) return TFGPU_ROW_CAST;
-      ((int64_t *)c.values)[r] = d;
-      return 0;
-    }
+  switch (c.out.kind) {
+    case SK_STR: c.lens[r] = 0; c.fstart[r] = nil ? 0u : 0x7FFFFFFFu; break;
+    case SK_JSONNUM: c.lens[r] = nil ? 0u : 1u; c.fstart[r] = nil ? 0u : 0x7FFFFFFFu; break;  // float64(0) is json.Number("0"): a cell that is no byte range
+    default: store_default(c.out, r);
   }
 }
 
@@ -491,7 +395,7 @@ __global__ void __launch_bounds__(256) nginx_convert_cells(GtSet cast_tp, GtSet 
   const int32_t j = (int32_t)blockIdx.y;
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const NgCol &c = cols[j];
-  const bool text = c.kind == NK_STR || c.kind == NK_JSONNUM;
+  const bool text = c.out.kind == SK_STR || c.out.kind == SK_JSONNUM;
   bool valid = true;
   if (r < nrows) {
     if (status[r]) {  // no row: it contributes no text
@@ -508,10 +412,13 @@ __global__ void __launch_bounds__(256) nginx_convert_cells(GtSet cast_tp, GtSet 
         ng_store_default(c, r, true);
       } else if (c.mode == NGM_LAYOUT) {
         int64_t sec = 0; int32_t ns = 0;
-        if (gotime_parse_any(layout, fv, 0, n, &sec, &ns)) { ((int64_t *)c.values)[r] = sec; c.nanos[r] = ns; }  // a time.Time passes cast.ToTimeE as it is
+        if (gotime_parse_any(layout, fv, 0, n, &sec, &ns)) { ((int64_t *)c.out.values)[r] = sec; c.out.nanos[r] = ns; }  // a time.Time passes cast.ToTimeE as it is
         else key = ((uint32_t)j << 8) | (uint32_t)TFGPU_ROW_CAST;
-      } else {
-        const int rc = ng_strict_cell(c, cast_tp, p128, r, fv, n, pos);
+      } else {  // strictifyValue; text stays where it is
+        int rc = 0;
+        if (!text) rc = strict_cell(c.out, cast_tp, p128, r, fv, 0, n);
+        else if (c.out.kind == SK_JSONNUM && !json_number_ok(fv, 0, n)) rc = TFGPU_ROW_CAST;
+        else { c.lens[r] = n; c.fstart[r] = pos; }
         if (rc) key = (1u << 30) | ((uint32_t)j << 8) | (uint32_t)rc;
       }
       if (key) atomicMin(&errkey[r], key);
@@ -539,16 +446,6 @@ __global__ void __launch_bounds__(256) nginx_finish_rows(const NgCol *cols, int3
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(nbad, (uint32_t)__popcll(m));
 }
 
-__global__ void nginx_fill_row_index(uint64_t *out, const uint32_t *rank, int64_t n, uint64_t base) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n) out[r] = base + (uint64_t)rank[r];  // lineCounter: blank lines do not advance it, failed ones do
-}
-__global__ void nginx_fill_file_name(uint32_t *off, uint8_t *data, int64_t n, const uint8_t *text, uint32_t len) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r > n) return;
-  off[r] = (uint32_t)r * len;
-  if (r < n) for (uint32_t i = 0; i < len; i++) data[(uint64_t)r * len + i] = text[i];
-}
 // the error list, in line order: errpos = exclusive scan of the failed-line flags; what does not fit `cap` is counted only
 __global__ void nginx_emit_errors(const uint8_t *status, const int32_t *err_col, const uint32_t *errpos, const uint32_t *rank, int64_t n, uint64_t base, int64_t cap,
                                   tfgpu_row_error *out) {
@@ -592,7 +489,7 @@ static std::unique_ptr<tfgpu_dbatch> nginx_cells(const NgWalked &w, const tfgpu_
   const size_t vbytes = (size_t)((n1 + 63) / 64) * 8;
   std::vector<NgCol> cols;
   std::vector<int> str_col_index;                  // schema index of the k-th text column
-  std::vector<std::pair<int, int>> sys_cols;       // (schema index, 1 = __file_name | 2 = __row_index)
+  std::vector<int> sys_cols;                       // schema indices of __file_name / __row_index
   bool need_p128 = false;
   int si = 0;
   for (int i = 0; i < ncols; i++) {
@@ -600,9 +497,8 @@ static std::unique_ptr<tfgpu_dbatch> nginx_cells(const NgWalked &w, const tfgpu_
     DColumn d;
     d.name = sc.name ? sc.name : ""; d.dtype = sc.dtype;
     if (w.col_slot[(size_t)i] == -2) {
-      const int sys = d.name == "__file_name" ? 1 : 2;
-      d.repr = sys == 1 ? TFGPU_R_STRING : TFGPU_R_UINT64;
-      sys_cols.push_back({i, sys});
+      d.repr = d.name == "__file_name" ? TFGPU_R_STRING : TFGPU_R_UINT64;
+      sys_cols.push_back(i);
       db->cols.push_back(std::move(d));
       continue;
     }
@@ -610,36 +506,21 @@ static std::unique_ptr<tfgpu_dbatch> nginx_cells(const NgWalked &w, const tfgpu_
     c.slot = w.col_slot[(size_t)i];
     c.schema_col = i;
     c.mode = c.slot < 0 ? NGM_DEFAULT : NGM_STRICT;
-    switch (sc.dtype) {
-      case TFGPU_T_INT8: c.kind = NK_INT; c.width = 1; c.lo = INT8_MIN; c.hi = INT8_MAX; d.repr = TFGPU_R_INT8; break;
-      case TFGPU_T_INT16: c.kind = NK_INT; c.width = 2; c.lo = INT16_MIN; c.hi = INT16_MAX; d.repr = TFGPU_R_INT16; break;
-      case TFGPU_T_INT32: c.kind = NK_INT; c.width = 4; c.lo = INT32_MIN; c.hi = INT32_MAX; d.repr = TFGPU_R_INT32; break;
-      case TFGPU_T_INT64: c.kind = NK_INT; c.width = 8; c.lo = INT64_MIN; c.hi = INT64_MAX; d.repr = TFGPU_R_INT64; break;
-      case TFGPU_T_UINT8: c.kind = NK_UINT; c.width = 1; c.hi = UINT8_MAX; d.repr = TFGPU_R_UINT8; break;
-      case TFGPU_T_UINT16: c.kind = NK_UINT; c.width = 2; c.hi = UINT16_MAX; d.repr = TFGPU_R_UINT16; break;
-      case TFGPU_T_UINT32: c.kind = NK_UINT; c.width = 4; c.hi = UINT32_MAX; d.repr = TFGPU_R_UINT32; break;
-      case TFGPU_T_UINT64: c.kind = NK_UINT; c.width = 8; c.hi = ~0ull; d.repr = TFGPU_R_UINT64; break;
-      case TFGPU_T_BOOLEAN: c.kind = NK_BOOL; c.width = 1; d.repr = TFGPU_R_BOOL; break;
-      case TFGPU_T_DATE: case TFGPU_T_DATETIME: c.kind = NK_TIME; c.width = 8; d.repr = TFGPU_R_TIME; if (c.slot >= 0) c.mode = NGM_LAYOUT; break;
-      // a timestamp column is a plain string into Strictify: cast.ToTimeE's layouts and nothing else (the CSV reader's parseTimestampValue, which reads
-      // an integer as Unix seconds, is not on this path)
-      case TFGPU_T_TIMESTAMP: c.kind = NK_TIME; c.width = 8; d.repr = TFGPU_R_TIME; break;
-      case TFGPU_T_FLOAT32: c.kind = NK_F32; c.width = 4; d.repr = TFGPU_R_FLOAT32; need_p128 = true; break;
-      case TFGPU_T_FLOAT64: c.kind = NK_JSONNUM; d.repr = TFGPU_R_JSONNUM; break;
-      case TFGPU_T_UTF8: case TFGPU_T_ANY: c.kind = NK_STR; d.repr = TFGPU_R_STRING; break;
-      case TFGPU_T_BYTES: c.kind = NK_STR; d.repr = TFGPU_R_BYTES; break;
-      case TFGPU_T_INTERVAL: c.kind = NK_INTERVAL; c.width = 8; d.repr = TFGPU_R_DURATION; break;
-      default: throw Error(TFGPU_ERR_CONFIG, "nginx: cannot strictify value of unknown type (column " + d.name + ")");
-    }
-    if (c.kind == NK_STR || c.kind == NK_JSONNUM) {
+    d.repr = strict_describe(sc.dtype, c.out);
+    if (d.repr == TFGPU_R_INVALID) throw Error(TFGPU_ERR_CONFIG, "nginx: cannot strictify value of unknown type (column " + d.name + ")");
+    // date / datetime: time.Parse(timeLocalLayout).  A timestamp column is a plain string into Strictify: cast.ToTimeE's layouts and nothing else (the CSV
+    // reader's parseTimestampValue, which reads an integer as Unix seconds, is not on this path)
+    if ((sc.dtype == TFGPU_T_DATE || sc.dtype == TFGPU_T_DATETIME) && c.slot >= 0) c.mode = NGM_LAYOUT;
+    if (c.out.kind == SK_F32) need_p128 = true;
+    if (c.out.kind == SK_STR || c.out.kind == SK_JSONNUM) {
       c.lens = ptr<uint32_t>(lens_all) + (int64_t)si * seg_stride;
       c.fstart = ptr<uint32_t>(fstart_all) + (int64_t)si * fstride;
       str_col_index.push_back(i);
       si++;
     } else {
-      d.values = dalloc((size_t)n1 * (size_t)c.width + 64);
-      c.values = d.values->p;
-      if (d.repr == TFGPU_R_TIME) { d.nanos = dalloc((size_t)n1 * 4 + 64); c.nanos = ptr<int32_t>(d.nanos); }
+      d.values = dalloc((size_t)n1 * (size_t)c.out.width + 64);
+      c.out.values = d.values->p;
+      if (d.repr == TFGPU_R_TIME) { d.nanos = dalloc((size_t)n1 * 4 + 64); c.out.nanos = ptr<int32_t>(d.nanos); }
     }
     d.validity = dalloc(vbytes + 8);
     c.valid = reinterpret_cast<unsigned long long *>(d.validity->p);
@@ -652,21 +533,15 @@ static std::unique_ptr<tfgpu_dbatch> nginx_cells(const NgWalked &w, const tfgpu_
   Buf errpos = nrows ? dalloc((size_t)(nrows + 1) * 4 + 16) : dalloc_zero(16);  // u32[nrows + 1]: failed lines in front of line r; [nrows] = their number
   Buf bcols = upload_const(cols.data(), std::max<size_t>(cols.size(), 1) * sizeof(NgCol));
   if (nrows) {
-    // spf13/cast v1.7.1 StringToDate's list (caste.go timeFormats) in its order, as tfgpu_strictify compiles it; then timeLocalLayout
-    static const char *const CAST_LAYOUTS[] = {
-        "2006-01-02", "2006-01-02T15:04:05Z07:00", "2006-01-02T15:04:05", "Mon, 02 Jan 2006 15:04:05 -0700", "Mon, 02 Jan 2006 15:04:05 MST",
-        "02 Jan 06 15:04 -0700", "02 Jan 06 15:04 MST", "Monday, 02-Jan-06 15:04:05 MST", "2006-01-02 15:04:05.999999999 -0700 MST",
-        "2006-01-02T15:04:05-0700", "2006-01-02 15:04:05Z0700", "2006-01-02 15:04:05", "Mon Jan _2 15:04:05 2006", "Mon Jan _2 15:04:05 MST 2006",
-        "Mon Jan 02 15:04:05 -0700 2006", "2006-01-02 15:04:05Z07:00", "02 Jan 2006", "2006-01-02 15:04:05 -07:00", "2006-01-02 15:04:05 -0700",
-        "3:04PM", "Jan _2 15:04:05", "Jan _2 15:04:05.000", "Jan _2 15:04:05.000000", "Jan _2 15:04:05.000000000"};
-    std::vector<GtOp> gops; std::string glits; std::vector<uint16_t> gstart{0}, gnginx;
-    for (const char *l : CAST_LAYOUTS) { gotime_compile(l, gops, glits); gstart.push_back((uint16_t)gops.size()); }
+    // the cast layouts, then timeLocalLayout
+    std::vector<GtOp> gops; std::string glits; std::vector<uint16_t> gstart, gnginx;
+    append_cast_layouts(gops, glits, gstart);
     gnginx.push_back((uint16_t)gops.size());
     gotime_compile("02/Jan/2006:15:04:05 -0700", gops, glits);
     gnginx.push_back((uint16_t)gops.size());
     Buf bgops = upload_const(gops.data(), gops.size() * sizeof(GtOp)), bglits = upload_const(glits.data(), glits.size());
     Buf bgs = upload_const(gstart.data(), gstart.size() * 2), bgn = upload_const(gnginx.data(), gnginx.size() * 2);
-    const GtSet cast_tp{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgs), (int32_t)(sizeof CAST_LAYOUTS / sizeof *CAST_LAYOUTS)};
+    const GtSet cast_tp{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgs), N_CAST_LAYOUTS};
     const GtSet layout{ptr<GtOp>(bgops), ptr<uint8_t>(bglits), ptr<uint16_t>(bgn), 1};
     const uint64_t *p128 = need_p128 ? reinterpret_cast<const uint64_t *>(pow10_table() + 632) : nullptr;
     TF_HIP(hipMemsetAsync(errkey->p, 0xFF, (size_t)nrows * 4, st));
@@ -706,24 +581,10 @@ static std::unique_ptr<tfgpu_dbatch> nginx_cells(const NgWalked &w, const tfgpu_
     d.view = std::move(v);
   }
 
-  for (auto &sy : sys_cols) {  // constructCI :227-238
-    DColumn &d = db->cols[(size_t)sy.first];
-    if (sy.second == 2) {
-      d.values = dalloc((size_t)n1 * 8);
-      if (nrows) nginx_fill_row_index<<<blocks(nrows, 256), 256, 0, st>>>(ptr<uint64_t>(d.values), ptr<uint32_t>(w.rank), nrows, opts.row_number_base);
-    } else {
-      const std::string fn = opts.file_name ? opts.file_name : "";
-      Buf btext = upload_small(fn.data(), fn.size());
-      d.offsets = dalloc((size_t)(nrows + 1) * 4 + 16);
-      d.data_len = (uint64_t)fn.size() * (uint64_t)nrows;
-      if (d.data_len >> 32) throw Error(TFGPU_ERR_UNSUPPORTED, "nginx: __file_name column exceeds 4 GiB");
-      d.data = dalloc(d.data_len + 8);
-      nginx_fill_file_name<<<blocks(nrows + 1, 256), 256, 0, st>>>(ptr<uint32_t>(d.offsets), ptr<uint8_t>(d.data), nrows, ptr<uint8_t>(btext), (uint32_t)fn.size());
-    }
-    if (opts.hide_system_cols) {  // hideSystemCols: both stay nil
-      d.validity = dalloc_zero((size_t)(nrows + 7) / 8 + 8);
-      if (sy.second == 1) { d.data_len = 0; TF_HIP(hipMemsetAsync(d.offsets->p, 0, (size_t)(nrows + 1) * 4, st)); }
-    }
+  for (int i : sys_cols) {  // constructCI :227-238; lineCounter: blank lines do not advance it, failed ones do
+    std::string detail;
+    const int rc = fill_system_column(db->cols[(size_t)i], nrows, opts.file_name, opts.row_number_base, ptr<uint32_t>(w.rank), opts.hide_system_cols, &detail);
+    if (rc) throw Error(rc, "nginx: " + detail);
   }
   if (nerrs) *nerrs = ne;
   if (!hbad) return db;
