@@ -1,4 +1,4 @@
-"""One batch read from two lanes: the selection -> dense hand-over of tf::dense / tf::dense_locked (tf_transform.hip).
+"""One batch read from two lanes: the selection -> dense hand-over of tf::dense / tf::dense_locked (tf_rows.hip).
 
 filter_rows and skip_events hand their kept rows on as a selection (tfgpu_dbatch::pending); the first reader gathers them in place, and the
 gather is only QUEUED on the gathering lane's stream.  A reader on another lane has to order its stream behind it (the lane's dense_event).

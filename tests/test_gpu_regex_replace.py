@@ -219,6 +219,30 @@ def test_input_that_is_still_a_selection(tf, oracle):
     assert_same(tf.apply_chain([f, t], tf.DeviceBatch.upload(b)).transformed.download(), want, "chain")
 
 
+def test_rows_with_their_own_column_names_are_refused(tf):
+    """The rule is positional (the i-th value against the i-th schema column): a batch with an ABSENT cell, and one whose rows carry their own
+    ColumnNames order, are refused by name before anything is computed (apply_plan's entry protocol) — mask_field, which walks each row's
+    own names, still takes the first and refuses only the second."""
+    from collapse_cases import batch_from_items
+    col = text_column("s", "utf8", abi.R_STRING, [b"ab", None, b"cd"])
+    col.absent = np.array([False, True, False])   # row 1 does not list the column (it reads nil)
+    ragged = tf.DeviceBatch.upload(abi.Batch([col], 3, "db", "t"))
+    items = [{"kind": "update", "keys": ["id"], "names": ["id", "b"], "values": [["int64", 1], ["string", "b0"]]},
+             {"kind": "update", "keys": ["id"], "names": ["id", "s"], "values": [["int64", 1], ["string", "a1"]]}]
+    ordered = tf.collapse(tf.DeviceBatch.upload(batch_from_items(items, names=["id", "s", "b"])[0]))   # merged names id, b, s: not the batch's order
+    assert ordered.download().col_order.tolist() == [[0, 2, 1]]
+    rx, mask = tf.Transformer(T, CFG), tf.Transformer("mask_field", {"columns": ["s"], "maskFunctionHash": {"userDefinedSalt": "salt"}})
+    for db in (ragged, ordered):
+        with pytest.raises(tf.TfgpuError, match="ABSENT cells") as e:
+            rx.apply(db)
+        assert e.value.code == tf.ERR_UNSUPPORTED
+    got = mask.apply(ragged).transformed.download()
+    assert got.nrows == 3 and got.cols[0].absent.tolist() == [False, True, False] and [len(got.cols[0].get_bytes(i)) for i in (0, 2)] == [64, 64]
+    with pytest.raises(tf.TfgpuError, match="ABSENT cells") as e:
+        mask.apply(ordered)
+    assert e.value.code == tf.ERR_UNSUPPORTED
+
+
 def test_chain_to_json_each_row(tf, oracle):
     n = 257
     cells = [CELLS[i % len(CELLS)] for i in range(n)]

@@ -85,7 +85,7 @@ def test_expression_types_and_schema_refusals(oracle):
 
 
 def test_city_hash64_restatement_agrees_with_itself():
-    """CityHash64 v1.0.2 is restated twice (oracle: Python integers; device: tf_transform.hip) from the published algorithm; the
+    """CityHash64 v1.0.2 is restated twice (oracle: Python integers; device: tf_sqleval.hip) from the published algorithm; the
     only value known without a ClickHouse run is the empty string's (k2).  The device side is compared in test_general_expressions."""
     from oracle import ora_sql
     assert ora_sql.city_hash64(b"") == 0x9AE16A3B2F90404F

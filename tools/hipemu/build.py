@@ -6,6 +6,7 @@ TEST INFRASTRUCTURE ONLY: a way to run the lane-per-item kernels' logic in the G
 tests/test_hipemu.py loads the result; transferia_amd/ never does (it has no CPU path)."""
 import os
 import re
+import runpy
 import subprocess
 import sys
 
@@ -14,8 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "transferia_amd", "csrc")
 SANITIZE = os.environ.get("HIPEMU_SANITIZE") == "1"   # AddressSanitizer + UBSan build (tools/hipemu/run_gpu_tests.py under LD_PRELOAD=libasan): hostile-input runs
 OUT = os.path.join(HERE, "_build_asan" if SANITIZE else "_build")
-UNITS = ["tf_runtime.hip", "tf_shard.hip", "tf_scan.hip", "tf_plan.cpp", "tf_sql.cpp", "tf_transformation.cpp", "tf_pipeline.cpp", "tf_dbzrecv.cpp", "tf_protoschema.cpp", "tf_transform.hip", "tf_regex.hip", "tf_api.hip", "tf_csv.hip", "tf_strictify.hip", "tf_nginx.hip", "tf_parquet.hip", "tf_parquetw.hip", "tf_dbzemit.hip", "tf_serialize.hip", "tf_json.hip",
-         "tf_collapse.hip", "tf_srjson.hip", "tf_exchange.hip", "tf_sizeof.hip", "tf_chnative.hip", "tf_debezium.hip", "tf_protobuf.hip"]  # = transferia_amd/build.py SOURCES
+SOURCES = runpy.run_path(os.path.join(ROOT, "transferia_amd", "build.py"))["SOURCES"]  # the product's own list of units (that file imports nothing of the package)
 LAUNCH = re.compile(r"(\b[A-Za-z_][A-Za-z0-9_:]*(?:<[^<>;]*>)?)\s*<<<\s*([^;]*?)>>>\s*\(")
 
 
@@ -47,7 +47,7 @@ def build() -> str:
     os.makedirs(OUT, exist_ok=True)
     so = os.path.join(OUT, "libtfgpu_emu.so")
     srcs = []
-    for u in UNITS:
+    for u in SOURCES:
         with open(os.path.join(CSRC, u)) as f:
             text = rewrite(f.read())
         text = text.replace(", )", ")")  # kernels without arguments

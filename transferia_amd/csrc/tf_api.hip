@@ -1,9 +1,9 @@
 // tf_api.hip — the transformer half of the C ABI (include/tfgpu.h): plan
 // lifecycle, Suitable / ResultSchema, and Apply over a chain of plans.
 #include "tf_plan.hpp"
+#include "tf_rows.hpp"
 
 using namespace tf;
-namespace tf { std::unique_ptr<tfgpu_dbatch> partition_rows(const tfgpu_dbatch &in, int nparts, int64_t *counts); }
 
 #define TF_API_BEGIN try {
 #define TF_API_END                                                        \
@@ -184,7 +184,7 @@ int tfgpu_apply(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, tf
     ax.step = i;
     size_t before = ax.errs.size();
     for (int m : hopped[(size_t)q]) mask_precheck(*plans[m], *cur);  // what those masks would have refused comes first, as in the configured order
-    std::unique_ptr<tfgpu_dbatch> next = apply_step(*plans[i], *cur, ax);
+    std::unique_ptr<tfgpu_dbatch> next = apply_plan(*plans[i], *cur, ax);
     // errors are reported against rows of the ORIGINAL input batch
     if (ax.errs.size() > before && cur->src_row) {
       std::vector<int32_t> sr((size_t)cur->nrows);

@@ -34,10 +34,9 @@
 #include <algorithm>
 
 #include "tf_emit.hpp"
+#include "tf_rows.hpp"
 
 namespace tf {
-
-std::unique_ptr<tfgpu_dbatch> gather_rows(const tfgpu_dbatch &in, const Buf &sel, int64_t m);  // tf_transform.hip
 
 static inline unsigned cgrid(int64_t n) { return (unsigned)((n + 255) / 256); }
 static constexpr uint32_t NOKEY = 0xFFFFFFFFu;

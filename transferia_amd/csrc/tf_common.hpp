@@ -255,7 +255,12 @@ struct tfgpu_dbuf {
 };
 
 namespace tf {
-
+inline std::unique_ptr<tfgpu_dbatch> shallow_copy(const tfgpu_dbatch &in) { return std::make_unique<tfgpu_dbatch>(in); }  // (the buffers are shared)
+template <class F> void materialize_where(const tfgpu_dbatch &b, F pred) {  // materialize() for the columns of b that pred picks
+  std::vector<const DColumn *> need;
+  for (auto &c : b.cols) if (pred(c)) need.push_back(&c);
+  materialize(b, &need);
+}
 // ---- shared device primitives (tf_scan.hip) --------------------------------
 // out[i] = sum(in[0..i)), i in [0, n]; out has n+1 entries when `with_total`.
 // in/out may alias.  All on ctx().stream.

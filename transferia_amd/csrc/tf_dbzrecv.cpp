@@ -24,6 +24,7 @@
 
 #include "tf_common.hpp"
 #include "tf_plan.hpp"
+#include "tf_rows.hpp"
 
 namespace tf {
 namespace dbzrecv {
@@ -260,7 +261,6 @@ static int compile(const uint8_t *bytes, size_t len, std::vector<Field> &out, st
 using namespace tf;
 using namespace tf::dbzrecv;
 
-namespace tf { std::unique_ptr<tfgpu_dbatch> compact_rows(const tfgpu_dbatch &in, Buf keep); }  // tf_transform.hip
 namespace tf { namespace dbz { void dbz_trust_frames(bool on); void dbz_tentative_frames(bool on); bool dbz_last_parse_was_quick(); void dbz_lazy_frames(bool on, uint64_t h0, uint64_t h1); bool dbz_last_unpack_uniform(); } }
 
 struct tfgpu_dbz_schema {

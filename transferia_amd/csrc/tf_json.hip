@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "tf_common.hpp"
+#include "tf_rows.hpp"
 #include "tf_devfmt.hpp"
 #include "tf_devfloat.hpp"
 #include "tf_devparse.hpp"
@@ -43,7 +44,6 @@
 
 namespace tf {
 
-std::unique_ptr<tfgpu_dbatch> compact_rows(const tfgpu_dbatch &in, Buf keep);  // tf_transform.hip
 uint32_t newline_starts(const uint8_t *data, uint64_t len, Buf *out);           // tf_csv.hip
 
 enum JKind : int32_t { JK_INT, JK_UINT, JK_F64, JK_BOOL, JK_TEXT, JK_ANY, JK_DATETIME };

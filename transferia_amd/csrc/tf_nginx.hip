@@ -7,6 +7,7 @@
 #include <map>
 
 #include "tf_common.hpp"
+#include "tf_rows.hpp"
 #include "tf_devfmt.hpp"
 #include "tf_devparse.hpp"
 #include "tf_devfloat.hpp"
@@ -193,7 +194,6 @@ extern "C" void tfgpu_nginx_options_default(tfgpu_nginx_options *o) {
 // ---- device ---------------------------------------------------------------------------------------------------------------
 namespace tf {
 
-std::unique_ptr<tfgpu_dbatch> compact_rows(const tfgpu_dbatch &in, Buf keep);  // tf_transform.hip
 uint32_t newline_starts(const uint8_t *data, uint64_t len, Buf *out);           // tf_csv.hip
 const double *pow10_table();                                                     // tf_json.hip
 static constexpr uint8_t NG_BLANK = 0xFF;  // status of a line the reader skips (strings.TrimSpace(line) == ""): no row, no lineCounter

@@ -161,17 +161,19 @@ std::vector<SqlOut> sql_resolve(const tfgpu_plan &p, const std::vector<SchemaCol
 bool sql_where_as_tree(const tfgpu_plan &p, const std::vector<SchemaCol> &in);                        // the WHERE runs as the expression program over this schema
 std::vector<int> sql_node_types(const tfgpu_plan &p, const std::vector<SchemaCol> &in);               // ClickHouse type of every node that is reachable from an item / the WHERE (SQL_PENDING elsewhere)
 std::string type_name(int dtype);                                                                    // YT type name of a TFGPU_T_* code
-// Apply one plan to a device batch (tf_transform.hip). `errs` collects row errors.
+// Apply one plan to a device batch (tf_transform.hip: the one dispatcher, every kind behind one entry protocol). `errs` collects row errors.
 struct ApplyCtx {
   std::vector<tfgpu_row_error> errs;
   int step = 0;
 };
-// NOT for PK_REGEX_REPLACE (it throws `unknown plan kind`): chains go through apply_step below.  The one direct caller left replays mask_field
-// plans only (tf_transformation.cpp, the hopped masks).  A further plan kind belongs into apply_plan itself, with the profile stamp of
-// tf_transform.hip refreshed (tests/test_profiles_stamp.py), not into a third dispatcher.
 std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
-// apply_plan for the kinds tf_transform.hip runs, regex_replace_transformer through tf_regex.hip: what tfgpu_apply and the Push loop call per step
-std::unique_ptr<tfgpu_dbatch> apply_step(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
+std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch &in);  // the kinds with a unit of their own: tf_mask.hip, tf_sqleval.hip, tf_regex.hip
+std::unique_ptr<tfgpu_dbatch> apply_sql(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
+std::unique_ptr<tfgpu_dbatch> apply_regex_replace(const tfgpu_plan &p, const tfgpu_dbatch &in);
 void mask_precheck(const tfgpu_plan &p, const tfgpu_dbatch &in);  // throws what apply_mask would refuse for the whole batch
 std::vector<int> chain_sequence(const tfgpu_plan *const *plans, int n, std::vector<std::vector<int>> *hopped);  // see tf_transform.hip
+std::unique_ptr<tfgpu_dbatch> run_filter(const std::vector<FExpr> &exprs, bool table_applies, bool check_kinds, const tfgpu_dbatch &in, ApplyCtx &ax);  // these four: tf_transform.hip, for tf_sqleval.hip and tf_strictify.hip
+DColumn column_to_string(const DColumn &c, int64_t n, bool to_bytes, int max_len_hint, int nil_empty = 0);
+DColumn column_to_text(const DColumn &c, int64_t n, bool to_bytes);  // fmt's %v of integers, bools, time.Time, time.Duration = their strconv / String() forms
+bool todatetime_values(const DColumn &src, int64_t n, int64_t *out);
 }  // namespace tf

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "tf_common.hpp"
+#include "tf_rows.hpp"
 #include "tf_devfloat.hpp"
 #include "tf_devparse.hpp"
 #include "tf_emit.hpp"
@@ -389,7 +390,6 @@ template <bool WIDE> __global__ void __launch_bounds__(256) pb_text_any(Params p
 static inline unsigned nblk(int64_t n, int t) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
 
 }  // namespace pbd
-std::unique_ptr<tfgpu_dbatch> compact_rows(const tfgpu_dbatch &in, Buf keep);  // tf_transform.hip
 }  // namespace tf
 
 // 32-bit offsets hold less than 4 GiB per column.  TFGPU_TEST_TEXT_LIMIT (tests only) lowers the bound so that the refusal can be

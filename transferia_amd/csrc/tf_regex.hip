@@ -10,11 +10,9 @@
 
 #include "tf_plan.hpp"
 #include "tf_devcol.hpp"
+#include "tf_rows.hpp"
 
 namespace tf {
-
-std::unique_ptr<tfgpu_dbatch> gather_rows(const tfgpu_dbatch &in, const Buf &sel, int64_t m);  // tf_transform.hip
-void refuse_absent(const tfgpu_dbatch &b);                                                        // tf_transform.hip
 
 // ============================================================================
 // host: pattern → program
@@ -716,7 +714,7 @@ static Buf upload_prog(const RegexProg &rx, RxParams &rp) {
   return d;
 }
 
-static std::unique_ptr<tfgpu_dbatch> apply_regex_replace(const tfgpu_plan &p, const tfgpu_dbatch &in) {
+std::unique_ptr<tfgpu_dbatch> apply_regex_replace(const tfgpu_plan &p, const tfgpu_dbatch &in) {
   if (!p.tables.match(in.table)) {  // transformer.go:96-99: the loop `continue`s — the item is neither transformed nor an error
     Buf sel = dalloc(4);
     return gather_rows(in, sel, 0);
@@ -801,16 +799,6 @@ static std::unique_ptr<tfgpu_dbatch> apply_regex_replace(const tfgpu_plan &p, co
     c = std::move(o);
   }
   return out;
-}
-
-// One step of an Apply chain (the callers hold the lane's mutex and hand over their own snapshot of the batch, as for apply_plan).
-std::unique_ptr<tfgpu_dbatch> apply_step(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax) {
-  if (p.kind != PK_REGEX_REPLACE) return apply_plan(p, in, ax);
-  // the rule is positional (the i-th value against the i-th schema column): rows that list their own columns stay with the stock path
-  refuse_absent(in);
-  if (in.pending) dense_locked(in);  // a filter's kept rows: gathered first, as for every plan but mask_field
-  else dense(&in);                   // (dense already: only waits for a gather another lane may have queued; takes no lane mutex)
-  return apply_regex_replace(p, in);
 }
 
 }  // namespace tf

@@ -24,7 +24,7 @@
 // a literal.  Constants fold while the query is read.  The forms that had kernels of their own before the general tree (a column,
 // a constant, casts and ± literal over one column, toString / toDateTime of a column, a WHERE that is an OR of ANDs of column
 // against literal) are recognised in the tree and keep them; everything else runs the expression program (sql_expr_kernel,
-// tf_transform.hip).  Result columns map back to YT types through typesystem.go's Source rules
+// tf_sqleval.hip).  Result columns map back to YT types through typesystem.go's Source rules
 // (pkg/providers/clickhouse/typesystem.go:15-33: String → `string`, DateTime → `datetime`, …), and a result column is a
 // primary key when it carries the NAME of an input key column (clickhouse_local.go:393-421).
 //

@@ -54,7 +54,6 @@ int fill_system_column(DColumn &d, int64_t nrows, const char *file_name, uint64_
 
 enum StrictMode : int32_t { SM_TEXT = 1, SM_TEXT_JSONNUM_OUT = 2, SM_INTS = 3, SM_JSONNUM_TO_TIME = 4, SM_FAIL = 5 /* no conversion exists: every value fails */,
                             SM_FLOATS = 6 /* Go float64 / float32 values under integer / bool / float DataTypes */ };
-DColumn column_to_text(const DColumn &c, int64_t n, bool to_bytes);  // tf_transform.hip: fmt's %v of integers, bools, time.Time, time.Duration = their strconv / String() forms
 struct StrictCol {
   int32_t mode, src_repr;
   const void *values; const uint32_t *offsets; const uint8_t *data; const uint8_t *validity;

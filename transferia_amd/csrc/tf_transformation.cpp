@@ -12,12 +12,9 @@
 #include <thread>
 
 #include "tf_plan.hpp"
+#include "tf_rows.hpp"
 
 using namespace tf;
-namespace tf {
-std::unique_ptr<tfgpu_dbatch> gather_rows(const tfgpu_dbatch &in, const Buf &sel, int64_t m);  // tf_transform.hip
-void plan_result_columns(const tfgpu_plan &p, std::vector<SchemaCol> &cols);                    // tf_api.hip
-}
 
 #define TF_API_BEGIN try {
 #define TF_API_END                                                        \
@@ -97,7 +94,7 @@ static void push_run(tfgpu_transformation &t, const tfgpu_dbatch &in, const tfgp
     ApplyCtx ax;
     ax.step = pi;
     for (int m : hopped[q]) mask_precheck(*chain[(size_t)m], *cur);
-    std::unique_ptr<tfgpu_dbatch> next = apply_step(*t.transformers[(size_t)pi], *cur, ax);
+    std::unique_ptr<tfgpu_dbatch> next = apply_plan(*t.transformers[(size_t)pi], *cur, ax);
     if (!ax.errs.empty()) {
       std::vector<int32_t> rows(ax.errs.size());
       for (size_t k = 0; k < ax.errs.size(); k++) rows[k] = (int32_t)ax.errs[k].row;
