@@ -454,7 +454,16 @@ int tfgpu_host_free(void *p);
  * answers TFGPU_ERR_CONFIG ("unable to compile match regexp: ...").  Either
  * way the shim keeps the stock transformer.  replaceRule is Regexp.Expand's
  * template ($1, ${1}, $$; names expand to nothing).  It is not one of the ten
- * names tfgpu_registry_* lists (below).                                     */
+ * names tfgpu_registry_* lists (below).
+ * "table_splitter_transformer" (pkg/transformer/registry/table_splitter/
+ * table_splitter.go; config keys tables, columns — a LIST of names, in
+ * order —, splitter, useLegacyLf) has a device plan: Type, Description,
+ * Suitable and ResultSchema (the identity) as the reference has them.  It
+ * changes every row's Table, so its Apply is not tfgpu_apply (a batch is one
+ * table): tfgpu_table_split / tfgpu_apply_split below return the rows filed
+ * under their generated names.  useLegacyLf = true (generic_parser's
+ * TableSplitter with castx.ToStringE) answers TFGPU_ERR_UNSUPPORTED naming the
+ * key.  It is not one of the ten names of tfgpu_registry_* either.            */
 #define TFGPU_REGEX_MAX_PROG 128    /* instructions a pattern may compile to (repeats {n,m} are unrolled)      */
 #define TFGPU_REGEX_MAX_RANGES 256  /* (lo, hi) rune pairs of all its character classes together               */
 #define TFGPU_REGEX_MAX_GROUPS 16   /* capturing groups                                                         */
@@ -474,7 +483,7 @@ int tfgpu_plan_result_schema(const tfgpu_plan *plan, const tfgpu_schema *in, tfg
 void tfgpu_schema_free(tfgpu_schema *s);
 
 /* The first ten device transformer types and their names (mask_field ... sql).  The list is kept as it was first
- * published; types that got a device plan later (regex_replace_transformer) are not in it: tfgpu_plan_create is the
+ * published; types that got a device plan later (regex_replace_transformer, table_splitter_transformer) are not in it: tfgpu_plan_create is the
  * authority on whether a type has a device plan.                                                                    */
 int tfgpu_registry_count(void);
 const char *tfgpu_registry_name(int i);
@@ -501,6 +510,47 @@ void tfgpu_dbatch_free(tfgpu_dbatch *b);
  * `errs` (optional) receives up to `errs_cap` row errors; *nerrs the total.  */
 int tfgpu_apply(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, tfgpu_dbatch **out,
                 tfgpu_row_error *errs, int64_t errs_cap, int64_t *nerrs);
+
+/* ---- table_splitter_transformer: rows to per-table batches (transferia_amd/csrc/tf_tablesplit.hip) --------------------
+ * GenerateTableName (table_splitter.go:37-59) for every row: the batch's table name when it is not empty, then one
+ * SerializeToString (to_string.go:145-171, UTC conversion on) per configured column name that the batch's TableSchema has
+ * (its columns, when it carries no TableSchema), in config order — a name the schema lacks contributes nothing, a name
+ * configured twice contributes twice, a value the row does not have (a schema column the batch lacks, an ABSENT cell, a
+ * nil) prints "<nil>", "null" under DataType any — joined with `splitter` ("/" when empty).
+ * Rows with the same name form one table; tables are numbered in order of first appearance in the input, the order a
+ * sink's SplitByTableID meets them in.  Equal names are equal BYTES: two different value tuples that print alike
+ * ("a/b" + "c" and "a" + "b/c" under "/") are one table.
+ *   tfgpu_table_split   `plan` must be a table_splitter_transformer; `in` may still be a selection and may hold ABSENT cells.
+ *   tfgpu_apply_split   plans[0 .. nplans-2] exactly as tfgpu_apply runs them (row errors in errs, rows of the ORIGINAL
+ *                       batch), then plans[nplans-1], which must be the chain's only table splitter.
+ *   tfgpu_tablesplit_batch  table t as an ordinary batch every entry here accepts: its rows in input order, namespace = the
+ *                       input's, table = the generated name, kinds / OldKeys (with presence) / part_id / ABSENT bitmaps /
+ *                       TableSchema carried along, src_row = the row's index in the batch given to the call, composed with the
+ *                       src_row the front of the chain left.  Gathered on demand; the caller frees it; it stays valid after
+ *                       tfgpu_tablesplit_free.  (A name that holds a NUL byte is cut there by tfgpu_dbatch_view's C string;
+ *                       tfgpu_tablesplit_name has all of it.)
+ * The handle belongs to the lane that made it.  TFGPU_ERR_UNSUPPORTED, by name: a batch holding non-row kinds (TFGPU_K_OTHER,
+ * TFGPU_K_SYNCHRONIZE), a batch with col_order, more than 2^31 - 1 rows, names whose texts together reach 4 GiB, the value
+ * forms SerializeToString prints otherwise than the device does ([]byte under a non-"string" DataType, `any` holding Go
+ * strings, floats, times or durations).
+ * tfgpu_apply with a table splitter anywhere in the chain answers TFGPU_ERR_UNSUPPORTED naming tfgpu_apply_split — judged from the plans
+ * alone, before `in` / `out` are looked at (a chain holding a splitter gets this answer even with a NULL batch; every other chain's
+ * argument checks are what they were); so does
+ * tfgpu_apply_split with a splitter that is not last, or with two (the followers go over each table's batch: the caller runs
+ * tfgpu_apply over tfgpu_tablesplit_batch's results).  tfgpu_transformation_create / _from_config refuse a chain holding one
+ * ("unable to init: table_splitter_transformer: ..."): a Push whose result is several tables is not built yet, the shim keeps
+ * the stock chain.                                                                                                            */
+typedef struct tfgpu_tablesplit tfgpu_tablesplit;
+int tfgpu_table_split(const tfgpu_plan *plan, const tfgpu_dbatch *in, tfgpu_tablesplit **out);
+int tfgpu_apply_split(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, tfgpu_tablesplit **out,
+                      tfgpu_row_error *errs, int64_t errs_cap, int64_t *nerrs);
+int64_t tfgpu_tablesplit_rows(const tfgpu_tablesplit *s);
+int32_t tfgpu_tablesplit_count(const tfgpu_tablesplit *s);                                  /* distinct generated names */
+const char *tfgpu_tablesplit_name(const tfgpu_tablesplit *s, int32_t t, size_t *len);       /* bytes; may hold NULs */
+int tfgpu_tablesplit_table_rows(const tfgpu_tablesplit *s, int32_t t, int64_t *nrows);
+int tfgpu_tablesplit_row_tables(const tfgpu_tablesplit *s, int32_t *ids /* HOST [rows] */); /* table of every row, input order */
+int tfgpu_tablesplit_batch(const tfgpu_tablesplit *s, int32_t t, tfgpu_dbatch **out);
+void tfgpu_tablesplit_free(tfgpu_tablesplit *s);
 
 /* ---- transformation.Push (pkg/transformer/transformation.go:46-282) -------------------------------------------------
  * The stage middlewares.Transformation builds from Transfer.TransformationConfigs() + ExtraTransformers

@@ -58,6 +58,28 @@ void plan_result_columns(const tfgpu_plan &p, std::vector<SchemaCol> &cols) {
   }
   cols.swap(out);
 }
+std::unique_ptr<tfgpu_dbatch> run_chain(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch &in, ApplyCtx &ax) {
+  std::unique_ptr<tfgpu_dbatch> cur = tf::snapshot(in);  // (another lane may be making the handle dense: copied under that transition's lock)
+  // transformation.do (transformation.go:252-274): toApply = t.Apply(toApply).Transformed
+  std::vector<std::vector<int>> hopped;
+  const std::vector<int> seq = chain_sequence(plans, nplans, &hopped);  // a filter_rows in front of the mask_fields it does not read
+  for (int q = 0; q < nplans; q++) {
+    const int i = seq[(size_t)q];
+    ax.step = i;
+    size_t before = ax.errs.size();
+    for (int m : hopped[(size_t)q]) mask_precheck(*plans[m], *cur);  // what those masks would have refused comes first, as in the configured order
+    std::unique_ptr<tfgpu_dbatch> next = apply_plan(*plans[i], *cur, ax);
+    // errors are reported against rows of the ORIGINAL input batch
+    if (ax.errs.size() > before && cur->src_row) {
+      std::vector<int32_t> sr((size_t)cur->nrows);
+      d2h(sr.data(), cur->src_row->p, sr.size() * 4);
+      tf::sync();
+      for (size_t k = before; k < ax.errs.size(); k++) ax.errs[k].row = sr[(size_t)ax.errs[k].row];
+    }
+    cur = std::move(next);
+  }
+  return cur;
+}
 }  // namespace tf
 
 extern "C" {
@@ -146,7 +168,7 @@ int tfgpu_plan_result_schema(const tfgpu_plan *p, const tfgpu_schema *in, tfgpu_
       case PK_FILTER_COLUMNS:  // filter_columns_transformer.go:228-239
         if (!p->columns.match(name)) continue;
         break;
-      default: break;  // rename, skip_events, filter_rows, sharder: schema unchanged
+      default: break;  // rename, skip_events, filter_rows, sharder, table splitter: schema unchanged
     }
     tfgpu_colschema &o = s->cols[s->ncols++];
     o.name = dup_cstr(name); o.dtype = dtype; o.flags = c.flags;
@@ -172,28 +194,14 @@ void tfgpu_schema_free(tfgpu_schema *s) {
 int tfgpu_apply(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, tfgpu_dbatch **out, tfgpu_row_error *errs,
                 int64_t errs_cap, int64_t *nerrs) {
   TF_API_BEGIN
-  if (!in || !out || (nplans > 0 && !plans)) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply: null argument");
+  if (nplans > 0 && !plans) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply: null argument");
+  for (int i = 0; i < nplans; i++)  // (judged from the plans alone, before the batch is looked at)
+    if (plans[i] && plans[i]->kind == PK_TABLE_SPLITTER)
+      return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_apply: table_splitter_transformer files the rows under several tables and a batch is one table: run the chain with tfgpu_apply_split");
+  if (!in || !out) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply: null argument");
   std::lock_guard<std::mutex> lk(ctx().mu);
   ApplyCtx ax;
-  std::unique_ptr<tfgpu_dbatch> cur = tf::snapshot(*in);  // (another lane may be making the handle dense: copied under that transition's lock)
-  // transformation.do (transformation.go:252-274): toApply = t.Apply(toApply).Transformed
-  std::vector<std::vector<int>> hopped;
-  const std::vector<int> seq = chain_sequence(plans, nplans, &hopped);  // a filter_rows in front of the mask_fields it does not read
-  for (int q = 0; q < nplans; q++) {
-    const int i = seq[(size_t)q];
-    ax.step = i;
-    size_t before = ax.errs.size();
-    for (int m : hopped[(size_t)q]) mask_precheck(*plans[m], *cur);  // what those masks would have refused comes first, as in the configured order
-    std::unique_ptr<tfgpu_dbatch> next = apply_plan(*plans[i], *cur, ax);
-    // errors are reported against rows of the ORIGINAL input batch
-    if (ax.errs.size() > before && cur->src_row) {
-      std::vector<int32_t> sr((size_t)cur->nrows);
-      d2h(sr.data(), cur->src_row->p, sr.size() * 4);
-      tf::sync();
-      for (size_t k = before; k < ax.errs.size(); k++) ax.errs[k].row = sr[(size_t)ax.errs[k].row];
-    }
-    cur = std::move(next);
-  }
+  std::unique_ptr<tfgpu_dbatch> cur = run_chain(plans, nplans, *in, ax);
   if (nerrs) *nerrs = (int64_t)ax.errs.size();
   if (errs) for (int64_t k = 0; k < errs_cap && k < (int64_t)ax.errs.size(); k++) errs[k] = ax.errs[(size_t)k];
   *out = cur.release();

@@ -566,8 +566,15 @@ std::unique_ptr<tfgpu_plan> make_plan(const std::string &type_name, const std::s
     p->tables = tables_of(cfg); p->columns = columns_of(cfg);
     p->rx_pattern = cfg.s("regexMatch"); p->rx_rule = cfg.s("replaceRule");
     p->rx = std::make_shared<const RegexProg>(regex_compile(p->rx_pattern, p->rx_rule));
+  } else if (type_name == "table_splitter_transformer") {  // table_splitter/table_splitter.go:21-35, 61-66
+    p->kind = PK_TABLE_SPLITTER;
+    p->tables = tables_of(cfg); p->columns.init({}, {});
+    p->split_cols = cfg.strings("columns");
+    p->splitter = cfg.s("splitter");
+    if (cfg.flag("useLegacyLf"))
+      throw Error(TFGPU_ERR_UNSUPPORTED, "table_splitter_transformer useLegacyLf=true builds the name with generic_parser.TableSplitter and castx.ToStringE on the host; not a device transform");
   } else if (type_name == "lambda" || type_name == "dbt" || type_name == "logger" || type_name == "yt_dict_transformer" || type_name == "raw_doc_grouper" ||
-             type_name == "raw_cdc_doc_grouper" || type_name == "table_splitter_transformer" || type_name == "number_to_float_transformer" ||
+             type_name == "raw_cdc_doc_grouper" || type_name == "number_to_float_transformer" ||
              type_name == "problem_item_detector" || type_name == "batch_splitter" || type_name == "filter_strm_access_log" || type_name == "jsonparser" ||
              type_name == "filter_rows_by_ids" || type_name == "mongo_pk_extender") {
     // registered in the reference (pkg/transformer/registry/*), outside the device subset (out of scope)
@@ -631,6 +638,7 @@ bool plan_suitable(const tfgpu_plan &p, const std::string &ns, const std::string
     }
     case PK_SQL:  // clickhouse_local.go:335-349: the table filter decides; a result without columns / key is only warned about
       return p.tables.match_table(ns, name);
+    case PK_TABLE_SPLITTER: return p.tables.match_table(ns, name);  // table_splitter.go:96-98
     case PK_REGEX_REPLACE: return p.tables.match(name);  // transformer.go:64-66: the table's name alone, no namespace variants
     case PK_TO_DATETIME:  // to_datetime.go:63-76
       if (!p.tables.match_table(ns, name)) return false;
@@ -645,6 +653,12 @@ static std::string join(const std::vector<std::string> &v, const char *sep) {
   std::string o;
   for (size_t i = 0; i < v.size(); i++) { if (i) o += sep; o += v[i]; }
   return o;
+}
+// table_splitter.go:112-121: the cut form only when it is SHORTER than the value
+static std::string trim_and_more(const std::string &v, size_t keep) {
+  if (v.size() < keep) keep = v.size();
+  std::string t = v.substr(0, keep) + "... and " + std::to_string(v.size() - keep) + " more";
+  return t.size() < v.size() ? t : v;
 }
 static std::string trim100(std::string s) { if (s.size() > 100) s.resize(100); return s; }
 
@@ -671,6 +685,9 @@ std::string plan_description(const tfgpu_plan &p) {
       if (p.columns.empty()) return "Replace all string column values via regular expression";
       return "Replace given string column values (include: " + trim100(join(p.columns.include_src, "|")) + ", exclude: " + trim100(join(p.columns.exclude_src, "|")) +
              ") via regular expression `" + p.rx_pattern + "`";
+    case PK_TABLE_SPLITTER:  // table_splitter.go:104-110: `columns=(...)` is built from the tables' ExcludeRegexp, as the reference builds it
+      return "Table splitter for tables=(include: " + trim_and_more(join(p.tables.include_src, "|"), 100) + ", exclude: " + trim_and_more(join(p.tables.exclude_src, "|"), 100) +
+             "); columns=(" + trim_and_more(join(p.tables.exclude_src, ","), 100) + "); splitter=" + p.splitter;
     case PK_REPLACE_PK: return "Replace primary keys to: " + join_keys(p.new_keys) + " ";
     case PK_SHARDER:
       if (p.columns.empty()) return "Transform to shard tables by field values";

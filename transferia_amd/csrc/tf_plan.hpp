@@ -58,7 +58,7 @@ std::vector<FTerm> parse_filter(const std::string &src);  // throws Error(TFGPU_
 
 }  // namespace tf
 
-enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL, PK_REGEX_REPLACE };
+enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL, PK_REGEX_REPLACE, PK_TABLE_SPLITTER };
 
 namespace tf {
 // ---- `sql` transformer, device subset (tf_sql.cpp) ----------------------------------------------------------------------
@@ -132,6 +132,9 @@ struct tfgpu_plan {
   // regex_replace_transformer
   std::string rx_pattern, rx_rule;
   std::shared_ptr<const tf::RegexProg> rx;
+  // table_splitter_transformer (tf_tablesplit.hip)
+  std::vector<std::string> split_cols;  // `columns`: names, in config order (a name may repeat)
+  std::string splitter;                 // as configured: empty means "/" when a name is built, Description prints it as it is
   // replace_primary_key
   std::vector<std::string> new_keys;
   bool is_new_key(const std::string &n) const {
@@ -170,6 +173,8 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
 std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch &in);  // the kinds with a unit of their own: tf_mask.hip, tf_sqleval.hip, tf_regex.hip
 std::unique_ptr<tfgpu_dbatch> apply_sql(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
 std::unique_ptr<tfgpu_dbatch> apply_regex_replace(const tfgpu_plan &p, const tfgpu_dbatch &in);
+// plans[0 .. nplans) over a snapshot of `in`, the loop of tfgpu_apply (tf_api.hip; the caller holds the lane's mutex): for tfgpu_apply_split (tf_tablesplit.hip)
+std::unique_ptr<tfgpu_dbatch> run_chain(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch &in, ApplyCtx &ax);
 void mask_precheck(const tfgpu_plan &p, const tfgpu_dbatch &in);  // throws what apply_mask would refuse for the whole batch
 std::vector<int> chain_sequence(const tfgpu_plan *const *plans, int n, std::vector<std::vector<int>> *hopped);  // see tf_transform.hip
 std::unique_ptr<tfgpu_dbatch> run_filter(const std::vector<FExpr> &exprs, bool table_applies, bool check_kinds, const tfgpu_dbatch &in, ApplyCtx &ax);  // these four: tf_transform.hip, for tf_sqleval.hip and tf_strictify.hip

@@ -693,6 +693,8 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
   // the column droppers and the row filters carry the bitmaps.  `sql` (it serializes whole rows for clickhouse-local) and batches whose rows carry
   // their own name ORDER (col_order indexes the column list these transformers change) stay with the stock path.
   // regex_replace_transformer's rule is positional (the i-th value against the i-th schema column): rows that list their own columns stay with the stock path too.
+  if (p.kind == PK_TABLE_SPLITTER)
+    throw Error(TFGPU_ERR_UNSUPPORTED, "table_splitter_transformer files the rows under several tables and a batch is one table: it runs last, through tfgpu_apply_split");
   if (p.kind == PK_SQL || p.kind == PK_REGEX_REPLACE || (in.col_order && p.kind != PK_SHARDER)) refuse_absent(in);
   // `in` is the caller's OWN copy of the handle it was given (tfgpu_apply and push_run take it with snapshot(), under the transition's lock): nobody
   // else changes it.  A copy taken after another lane made the handle dense carries that lane's event: this lane's stream waits for it here.
@@ -710,6 +712,7 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
     case PK_REPLACE_PK: return apply_replace_pk(p, in);
     case PK_SQL: return apply_sql(p, in, ax);
     case PK_REGEX_REPLACE: return apply_regex_replace(p, in);
+    case PK_TABLE_SPLITTER: break;  // (refused above)
   }
   throw Error(TFGPU_ERR_INVALID, "unknown plan kind");
 }

@@ -258,13 +258,20 @@ std::string snakify(const std::string &in) {
 }
 }  // namespace
 
+// a Push whose result is several tables is not built: the chain as a whole stays with the stock transformers
+static void refuse_splitter(const tfgpu_plan *p) {
+  if (p->kind == PK_TABLE_SPLITTER)
+    throw tf::Error(TFGPU_ERR_UNSUPPORTED, "unable to init: table_splitter_transformer: its rows leave under several tables, which transformation.Push does not hand on yet "
+                                           "(tfgpu_apply_split runs it over one batch)");
+}
+
 extern "C" {
 
 int tfgpu_transformation_create(tfgpu_plan *const *transformers, int n, tfgpu_transformation **out) {
   TF_API_BEGIN
   if (!out || (n > 0 && !transformers)) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_transformation_create: null argument");
   auto t = std::make_unique<tfgpu_transformation>();
-  for (int i = 0; i < n; i++) { if (!transformers[i]) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_transformation_create: null transformer"); t->transformers.push_back(transformers[i]); }
+  for (int i = 0; i < n; i++) { if (!transformers[i]) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_transformation_create: null transformer"); refuse_splitter(transformers[i]); t->transformers.push_back(transformers[i]); }
   *out = t.release();
   return TFGPU_OK;
   TF_API_END
@@ -297,6 +304,7 @@ int tfgpu_transformation_from_config(const char *transformers_json, tfgpu_plan *
         const int rc = tfgpu_plan_create(type.c_str(), cfg.c_str(), &plan);
         if (rc) throw tf::Error(rc, "unable to init: " + type + ": " + tfgpu_last_error());  // middlewares/transformation.go:18-20
         t->owned.push_back(plan);
+        refuse_splitter(plan);
         t->transformers.push_back(plan);
         arr.ws();
         if (arr.p < arr.e && *arr.p == ',') { arr.p++; continue; }
@@ -309,7 +317,7 @@ int tfgpu_transformation_from_config(const char *transformers_json, tfgpu_plan *
       if (eo.p < eo.e && *eo.p == '{') eo.object([&](const std::string &name, const char *va, const char *vb) { if (name == "Type" || name == "type") { RawJson s{va, vb}; s.ws(); if (s.p < s.e && *s.p == '"') t->errors_output = s.str(); } });
     }
   });
-  for (int i = 0; i < n_extra; i++) { if (!extra[i]) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_transformation_from_config: null extra transformer"); t->transformers.push_back(extra[i]); }  // Transformation.ExtraTransformers
+  for (int i = 0; i < n_extra; i++) { if (!extra[i]) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_transformation_from_config: null extra transformer"); refuse_splitter(extra[i]); t->transformers.push_back(extra[i]); }  // Transformation.ExtraTransformers
   *out = t.release();
   return TFGPU_OK;
   TF_API_END

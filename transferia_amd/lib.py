@@ -34,6 +34,8 @@ EXPORTS = [
     "tfgpu_prof_get", "tfgpu_prof_get_units", "tfgpu_parquet_read_object", "tfgpu_parquet_staging_size", "tfgpu_parquet_read_staged", "tfgpu_parquet_resolve_schema", "tfgpu_dbatch_nrows", "tfgpu_dbatch_dense",
     "tfgpu_nginx_format_compile", "tfgpu_nginx_format_free", "tfgpu_nginx_format_ntokens", "tfgpu_nginx_format_token", "tfgpu_nginx_format_nfields", "tfgpu_nginx_format_field",
     "tfgpu_nginx_resolve_schema", "tfgpu_nginx_options_default", "tfgpu_nginx_parse", "tfgpu_nginx_tile_bytes", "tfgpu_nginx_workgroup_lines",
+    "tfgpu_table_split", "tfgpu_apply_split", "tfgpu_tablesplit_rows", "tfgpu_tablesplit_count", "tfgpu_tablesplit_name", "tfgpu_tablesplit_table_rows",
+    "tfgpu_tablesplit_row_tables", "tfgpu_tablesplit_batch", "tfgpu_tablesplit_free",
 ]
 
 
@@ -152,6 +154,19 @@ def load():
     L.tfgpu_nginx_options_default.restype = None
     L.tfgpu_nginx_parse.argtypes = [P, C.POINTER(abi.CNginxOptions), C.POINTER(abi.CSchema), P, C.c_uint64, C.c_int, C.POINTER(P), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64), C.POINTER(abi.CRowError), C.c_int64, C.POINTER(C.c_int64)]
+    L.tfgpu_table_split.argtypes = [P, P, C.POINTER(P)]
+    L.tfgpu_apply_split.argtypes = [C.POINTER(P), C.c_int, P, C.POINTER(P), C.POINTER(abi.CRowError), C.c_int64, C.POINTER(C.c_int64)]
+    L.tfgpu_tablesplit_rows.restype = C.c_int64
+    L.tfgpu_tablesplit_rows.argtypes = [P]
+    L.tfgpu_tablesplit_count.restype = C.c_int32
+    L.tfgpu_tablesplit_count.argtypes = [P]
+    L.tfgpu_tablesplit_name.restype = P  # bytes that may hold NULs: read with string_at and the length
+    L.tfgpu_tablesplit_name.argtypes = [P, C.c_int32, C.POINTER(C.c_size_t)]
+    L.tfgpu_tablesplit_table_rows.argtypes = [P, C.c_int32, C.POINTER(C.c_int64)]
+    L.tfgpu_tablesplit_row_tables.argtypes = [P, P]
+    L.tfgpu_tablesplit_batch.argtypes = [P, C.c_int32, C.POINTER(P)]
+    L.tfgpu_tablesplit_free.argtypes = [P]
+    L.tfgpu_tablesplit_free.restype = None
     _lib = L
     return L
 
@@ -445,7 +460,8 @@ class DeviceBatch:
                 col.validity = abi.unpack_validity(col._bm, n)
             if hasattr(col, "_ab"):
                 col.absent = abi.unpack_validity(col._ab, n)
-        b = abi.Batch(cols[: v.ncols], n, (v.table_ns or b"").decode(), (v.table_name or b"").decode())
+        # (a table_splitter_transformer's generated name holds the cells' own bytes, valid UTF-8 or not)
+        b = abi.Batch(cols[: v.ncols], n, (v.table_ns or b"").decode(), (v.table_name or b"").decode("utf-8", "surrogateescape"))
         if nold:
             b.old_keys = cols[v.ncols:]
             b.old_present = abi.unpack_validity(opres, n) if opres is not None else np.ones(n, bool)
@@ -603,6 +619,82 @@ def apply_chain(transformers: Sequence[Transformer], batch: DeviceBatch, max_err
     el = [(int(errs[i].row), abi.ROWERR.get(int(errs[i].code), str(errs[i].code)), int(errs[i].step), int(errs[i].column))
           for i in range(min(int(nerr.value), max_errors))]
     return TransformerResult(DeviceBatch(out), el)
+
+
+class TableSplit:
+    """What table_splitter_transformer leaves of one batch (tfgpu_tablesplit): the generated table names in order of first appearance,
+    every row's table, and each table's rows as a DeviceBatch gathered when it is asked for."""
+
+    def __init__(self, handle, errors=()):
+        self._h = handle
+        self.errors = list(errors)  # the row errors of the transformers in front (apply_split)
+
+    @property
+    def nrows(self) -> int:
+        return int(load().tfgpu_tablesplit_rows(self._h))
+
+    @property
+    def count(self) -> int:
+        return int(load().tfgpu_tablesplit_count(self._h))
+
+    def name(self, t: int) -> bytes:
+        n = C.c_size_t(0)
+        p = load().tfgpu_tablesplit_name(self._h, int(t), C.byref(n))
+        if p is None and n.value == 0 and not 0 <= t < self.count:
+            raise IndexError(t)
+        return C.string_at(p, n.value) if n.value else b""
+
+    def names(self) -> List[bytes]:
+        return [self.name(t) for t in range(self.count)]
+
+    def table_rows(self, t: int) -> int:
+        n = C.c_int64(0)
+        _check(load().tfgpu_tablesplit_table_rows(self._h, int(t), C.byref(n)))
+        return int(n.value)
+
+    def row_tables(self) -> np.ndarray:
+        """the table of every input row, in input order"""
+        ids = np.zeros(max(self.nrows, 1), np.int32)
+        _check(load().tfgpu_tablesplit_row_tables(self._h, ids.ctypes.data_as(C.c_void_p)))
+        return ids[: self.nrows]
+
+    def batch(self, t: int) -> DeviceBatch:
+        h = C.c_void_p()
+        _check(load().tfgpu_tablesplit_batch(self._h, int(t), C.byref(h)))
+        return DeviceBatch(h)
+
+    def free(self):
+        if self._h:
+            load().tfgpu_tablesplit_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def table_split(transformer: Transformer, batch: DeviceBatch) -> TableSplit:
+    """tfgpu_table_split: a table_splitter_transformer's Apply over one batch."""
+    init()
+    h = C.c_void_p()
+    _check(load().tfgpu_table_split(transformer._h, batch._h, C.byref(h)))
+    return TableSplit(h)
+
+
+def apply_split(transformers: Sequence[Transformer], batch: DeviceBatch, max_errors: int = 1 << 16) -> TableSplit:
+    """tfgpu_apply_split: transformers[:-1] as apply_chain runs them, then transformers[-1], the chain's only table splitter."""
+    init()
+    n = len(transformers)
+    arr = (C.c_void_p * max(n, 1))(*[t._h for t in transformers])
+    h = C.c_void_p()
+    errs = _errbuf(max_errors)
+    nerr = C.c_int64(0)
+    _check(load().tfgpu_apply_split(arr, n, batch._h, C.byref(h), errs, max_errors, C.byref(nerr)))
+    el = [(int(errs[i].row), abi.ROWERR.get(int(errs[i].code), str(errs[i].code)), int(errs[i].step), int(errs[i].column))
+          for i in range(min(int(nerr.value), max_errors))]
+    return TableSplit(h, el)
 
 
 class PushResult:
