@@ -1,7 +1,9 @@
 """tfgpu_parquet_read (tf_parquet.hip) against an independent reader: files written by pyarrow in the shapes real writers produce —
 dictionary pages with RLE / bit-packed indices, PLAIN fall-back pages, optional columns (definition levels), data pages v1 and v2,
 several row groups, tiny and large pages — and read back by pyarrow.  PARITY UNPINNED against the reference (no .parquet input in
-its tree, parquet-go not vendored): what is checked is that every value and every null equals what pyarrow reads."""
+its tree, parquet-go not vendored): what is checked is that every value and every null equals what pyarrow reads.
+A writer emits a narrow dialect of each format; the rest of what the page kernels implement (pq_inflate, pq_hybrid, pq_delta) is read from
+hand-built pages in tests/test_gpu_parquet_pages.py (the builders: tests/parquet_hand.py, pinned to pyarrow by tests/test_parquet_hand.py)."""
 import io
 import os
 import struct
@@ -535,15 +537,17 @@ def _inflate_cases(tf, codec, n, check_kws, big_kws, damage_step, forced=True):
     assert failed > 0
 
 
-@pytest.mark.parametrize("mode", ["1", "auto"])
+@pytest.mark.parametrize("mode,ring", [pytest.param("1", 64, id="1"), pytest.param("1", 32, id="1-ring32"), pytest.param("1", 16, id="1-ring16"), pytest.param("auto", 64, id="auto")])
 @pytest.mark.parametrize("codec", ["SNAPPY", "LZ4_RAW"])
-def test_pages_inflated_on_the_device(tf, codec, mode, monkeypatch):
+def test_pages_inflated_on_the_device(tf, codec, mode, ring, monkeypatch):
     """pq_inflate (one wave a page; SNAPPY and LZ4_RAW): the shapes of `check` (dictionary pages + indices, PLAIN pages, v2 pages with their levels outside
     the compressed part, optional columns whose levels the host inflates as a prefix), pages larger than the 64 KiB LDS ring (repetitive text whose
     copies reach back over the ring, incompressible bytes = long literals, period-1 overlapping copies) and damaged pages — equal to pyarrow's reading."""
     # mode "1": every eligible page on the device (the kernel meets text, copies over the whole ring, damaged elements); "auto" (the default): pages that
-    # barely compress on the device — the noise column here — and the others on the host's cores, inflated side by side ahead of the walk
+    # barely compress on the device — the noise column here — and the others on the host's cores, inflated side by side ahead of the walk.
+    # ring: the LDS ring of pq_inflate (TFGPU_PQ_RING_KB, read per call) — with 16 and 32 KiB the text pages' far copies are read back from the image
     monkeypatch.setenv("TFGPU_PQ_DEVICE_INFLATE", mode)
+    monkeypatch.setenv("TFGPU_PQ_RING_KB", str(ring))
     _inflate_cases(tf, codec, 2600, ({}, {"use_dictionary": False, "data_page_version": "2.0", "row_group_size": 1500}),
                    ({"use_dictionary": False, "data_page_size": 1 << 24},), 11, forced=mode == "1")
 
