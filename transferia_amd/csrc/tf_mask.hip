@@ -38,6 +38,7 @@ struct MaskParams {
   uint32_t ipad[8], opad[8];
   int64_t nrows;
   uint8_t *out;  // nrows * 64 hex bytes
+  uint32_t *offsets;  // nrows + 1 Arrow offsets of the digests: 64 * r
   const int32_t *sel;  // non-null: output row r hashes the column's row sel[r] (the batch's rows are still a selection)
 };
 
@@ -138,11 +139,9 @@ __global__ void __launch_bounds__(256) mask_hmac_kernel(MaskParams p) {
     }
     dst[q] = make_uint4(o[0], o[1], o[2], o[3]);
   }
-}
-
-__global__ void fill_offsets_stride_kernel(uint32_t *off, int64_t n, uint32_t stride) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i <= n) off[i] = (uint32_t)(i * stride);
+  // every digest is 64 bytes: the column's offsets need no launch of their own (the last row's thread also writes offsets[nrows])
+  p.offsets[ro] = (uint32_t)(ro * 64);
+  if (ro == p.nrows - 1) p.offsets[p.nrows] = (uint32_t)(p.nrows * 64);
 }
 
 
@@ -183,12 +182,12 @@ std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch
     mp.col = dcol_of(c);
     std::memcpy(mp.ipad, p.ipad_state, sizeof mp.ipad);
     std::memcpy(mp.opad, p.opad_state, sizeof mp.opad);
-    mp.nrows = n; mp.out = ptr<uint8_t>(o.data); mp.sel = through;
+    mp.nrows = n; mp.out = ptr<uint8_t>(o.data); mp.offsets = ptr<uint32_t>(o.offsets); mp.sel = through;
     {
       KernelTimer t("mask_hmac_sha256", n);
       if (n) mask_hmac_kernel<<<grid_for(n, 256), 256, 0, st>>>(mp);
     }
-    fill_offsets_stride_kernel<<<grid_for(n + 1, 256), 256, 0, st>>>(ptr<uint32_t>(o.offsets), n, 64);
+    if (!n) TF_HIP(hipMemsetAsync(o.offsets->p, 0, 4, st));  // (an empty batch: offsets[0] alone)
     return o;
   };
   if (!in.pending) {

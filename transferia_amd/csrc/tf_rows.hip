@@ -241,10 +241,14 @@ static bool lazy_rows_on() {
 // over `in` (tfgpu_dbatch::pending) and gathered when — and if — somebody reads them.
 std::unique_ptr<tfgpu_dbatch> compact(const tfgpu_dbatch &in, Buf keep /* n+1 u32 */, bool lazy) {
   int64_t n = in.nrows;
-  exclusive_scan_u32(ptr<uint32_t>(keep), ptr<uint32_t>(keep), n, true);
-  const uint32_t *hm = d2h_u32(ptr<uint32_t>(keep) + n);
   Buf sel = dalloc((size_t)n * 4 + 4);  // sized for every row: the selection is built while the count travels to the host
-  if (n) build_selection_kernel<<<grid_for(n, 256), 256, 0, ctx().stream>>>(ptr<uint32_t>(keep), n, ptr<int32_t>(sel));
+  const uint32_t *hm;
+  if (select_kept_u32(ptr<uint32_t>(keep), n, ptr<int32_t>(sel), ptr<uint32_t>(keep) + n)) hm = d2h_u32(ptr<uint32_t>(keep) + n);
+  else {  // an empty batch, or one too long for the two-launch form: the scan, then the selection from the scan
+    exclusive_scan_u32(ptr<uint32_t>(keep), ptr<uint32_t>(keep), n, true);
+    hm = d2h_u32(ptr<uint32_t>(keep) + n);
+    if (n) build_selection_kernel<<<grid_for(n, 256), 256, 0, ctx().stream>>>(ptr<uint32_t>(keep), n, ptr<int32_t>(sel));
+  }
   sync();
   const uint32_t m = *hm;
   if ((int64_t)m == n) return shallow_copy(in);
