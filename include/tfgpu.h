@@ -1159,6 +1159,43 @@ typedef struct tfgpu_row_meta {
   int32_t mem;                   /* TFGPU_MEM_HOST / TFGPU_MEM_DEVICE                               */
 } tfgpu_row_meta;
 
+/* ---- raw_doc_grouper: rows to keys plus one JSON doc (transferia_amd/csrc/tf_rawdoc.hip) ------------------------------------
+ * tfgpu_plan_create("raw_doc_grouper", cfg) takes the Go config (pkg/transformer/registry/raw_doc_grouper/raw_doc_grouper.go:39-44:
+ * tables, keys, fields, shouldUpdateOldKeys) and applies NewRawDocGroupTransformer's rules: etl_updated_at and doc are appended to
+ * `fields` where neither list names them; a key listed twice, a name that is key and field, a bad table regexp are TFGPU_ERR_CONFIG
+ * with the Go texts.  shouldUpdateOldKeys = true is TFGPU_ERR_UNSUPPORTED by name: processUpdateItem then gives every Update row its own
+ * OldKeys name list (ragged OldKeys), which a tfgpu_batch cannot express.  Suitable = MatchAnyTableNameVariant and containsAllFields over
+ * the schema's names; tfgpu_plan_result_schema = resultSchema: the keys in config order with TFGPU_COL_KEY set, the fields with it cleared,
+ * an existing column's other ColSchema fields kept, etl_updated_at a `timestamp` and doc an `any` stub whose OriginalType is
+ * "pg:timestamp without time zone" / "pg:json" when some input column's OriginalType contains "pg:".  raw_cdc_doc_grouper stays refused.
+ *
+ * tfgpu_apply_meta is tfgpu_apply with the rows' CommitTime in reach; a chain that holds a raw_doc_grouper runs ONLY through it
+ * (tfgpu_apply and tfgpu_apply_split answer TFGPU_ERR_UNSUPPORTED naming this entry, judged from the plans alone;
+ * tfgpu_transformation_create / _from_config answer "unable to init: raw_doc_grouper: ..." until Push carries row meta).  Only
+ * meta->commit_time is read: row r of the batch a grouper sees reads entry src_row[r] (identity without src_row), so a filter_rows in
+ * front works; meta == NULL or commit_time == NULL is the Go zero value in every row; `mem` may be HOST or DEVICE; a src_row at or beyond
+ * meta->n is TFGPU_ERR_INVALID.  Every other chain behaves under it exactly as under tfgpu_apply.
+ *
+ * The grouper's output: namespace and table as they were; the input columns named in keys or fields, in INPUT order, sharing the input's
+ * buffers; then etl_updated_at = time.Unix(0, int64(CommitTime)) (timestamp, TFGPU_R_TIME: floor division of the nanoseconds, a
+ * CommitTime of 2^63 and more is a negative instant; Location is the shim's concern); then doc (any, TFGPU_R_JSON) = json.Marshal of
+ * the row's docData: compact, members in byte order of the key, no HTML escaping, every value as the encoding/json serializer prints
+ * the cell.  A row's members are the columns it lists: an ABSENT cell contributes nothing, a nil is null, a row that lists nothing is {}.
+ * `_rest`: a TFGPU_R_JSON cell of a column named `_rest` whose text starts with '{' IS the reference's map[string]interface{} — the ABI's
+ * contract for an `any` value: json.Marshal's text, one compact object, its keys ascending (what the generic parser's AddRest produces).
+ * Its members are spliced into the doc and the `_rest` key does not appear; on an equal key a column that stands BEHIND `_rest` in the
+ * batch wins if the row lists it, a column in FRONT of it loses to the rest member (Go's map overwrite in ColumnNames order).  Any other
+ * `_rest` value (nil, an array, a string, another repr) is the member "_rest".  TableSchema and key names are the result schema above;
+ * kinds, OldKeys, old_keys_present, part_id, src_row and the ABSENT bitmaps of the kept columns are carried.  An OldKeys column whose
+ * name the result does not list (inPlaceRemoveOldKeys touches Update rows only) is dropped when every row with OldKeys is an Update,
+ * kept when none is, and refused as ragged OldKeys when the batch mixes the two.
+ * Whole-call refusals, each TFGPU_ERR_UNSUPPORTED by name with nothing written: non-row kinds; col_order; an input column already named
+ * etl_updated_at or doc; a NaN / Inf float cell (the column and the first such row are named); a spliced `_rest` member key that holds
+ * a backslash, or a `_rest` text that is not one object; ragged OldKeys; a doc column reaching 4 GiB.  A batch whose TableSchema lacks
+ * a configured key or field is not an error of the call: every row goes to errs with TFGPU_ROW_COLUMN_NOT_FOUND and *out has no rows. */
+int tfgpu_apply_meta(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, const tfgpu_row_meta *meta, tfgpu_dbatch **out,
+                     tfgpu_row_error *errs, int64_t errs_cap, int64_t *nerrs);
+
 enum {
   TFGPU_QFMT_NATIVE = 1, /* NativeSerializer: "[" + ChangeItem.ToJSONString() + "]", batches joined by ","
                             (native_serializer.go:14-26, native_batcher.go:10-63; MarshalJSON change_item.go:568-616) */

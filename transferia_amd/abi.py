@@ -301,6 +301,14 @@ def row_meta(n, ids=None, lsns=None, commit_times=None, counters=None, tx_ids=No
     return m
 
 
+def row_meta_device(n, commit_time=None) -> CRowMeta:
+    """A tfgpu_row_meta whose arrays are DEVICE pointers the caller keeps alive (tfgpu_apply_meta reads commit_time only)."""
+    m = CRowMeta()
+    m.commit_time = int(commit_time) if commit_time else None
+    m.n, m.mem = int(n), MEM_DEVICE
+    return m
+
+
 def queue_options(fmt, enabled=False, max_change_items=0, max_message_size=0, table_schema_json=None, table_schema: "Schema" = None,
                   omit_table_schema=False, old_key_types=None, group_rows=None, group_part_ids=None) -> CQueueOptions:
     """model.Batching + what ChangeItem.MarshalJSON needs beyond the batch (queue serializers)."""

@@ -137,6 +137,33 @@ int tfgpu_plan_result_schema(const tfgpu_plan *p, const tfgpu_schema *in, tfgpu_
     *out = rs;
     return TFGPU_OK;
   }
+  if (p->kind == PK_RAW_DOC_GROUPER) {  // resultSchema / CollectFieldsForTransformer (raw_doc_grouper.go:129-152, raw_data_utils.go:22-69): keys, then fields
+    bool pg = false;  // getOriginalType: data from pg — some column's OriginalType holds "pg:"
+    for (int i = 0; i < in->ncols; i++) if (in->cols[i].original_type && std::strstr(in->cols[i].original_type, "pg:")) pg = true;
+    auto *rs = (tfgpu_schema *)std::calloc(1, sizeof(tfgpu_schema));
+    rs->cols = (tfgpu_colschema *)std::calloc(std::max<size_t>(p->rd_keys.size() + p->rd_fields.size(), 1), sizeof(tfgpu_colschema));
+    for (int is_key = 1; is_key >= 0; is_key--)
+      for (auto &name : is_key ? p->rd_keys : p->rd_fields) {
+        int at = -1;
+        for (int i = 0; i < in->ncols; i++) if (name == (in->cols[i].name ? in->cols[i].name : "")) at = i;  // MakeMapColNameToIndex: the last of that name
+        if (at < 0 && !rawdoc_special(name)) continue;
+        tfgpu_colschema &o = rs->cols[rs->ncols++];
+        if (at >= 0) {  // the column's own ColSchema, PrimaryKey rewritten
+          const tfgpu_colschema &c = in->cols[at];
+          o.name = dup_cstr(name); o.dtype = c.dtype; o.flags = is_key ? (c.flags | TFGPU_COL_KEY) : (c.flags & ~(uint32_t)TFGPU_COL_KEY);
+          o.path = dup_cstr(c.path ? c.path : ""); o.original_type = dup_cstr(c.original_type ? c.original_type : "");
+          o.table_schema = dup_cstr(c.table_schema ? c.table_schema : ""); o.table_name = dup_cstr(c.table_name ? c.table_name : "");
+          o.expression = dup_cstr(c.expression ? c.expression : ""); o.properties_json = c.properties_json ? dup_cstr(c.properties_json) : nullptr;
+        } else {  // MakeStubFieldWithOriginalType
+          const bool ts = name == "etl_updated_at";
+          o.name = dup_cstr(name); o.dtype = ts ? TFGPU_T_TIMESTAMP : TFGPU_T_ANY; o.flags = is_key ? TFGPU_COL_KEY : 0u;
+          o.path = dup_cstr(""); o.original_type = dup_cstr(!pg ? "" : ts ? "pg:timestamp without time zone" : "pg:json");
+          o.table_schema = dup_cstr(""); o.table_name = dup_cstr(""); o.expression = dup_cstr(""); o.properties_json = nullptr;
+        }
+      }
+    *out = rs;
+    return TFGPU_OK;
+  }
   auto *s = (tfgpu_schema *)std::calloc(1, sizeof(tfgpu_schema));
   s->cols = (tfgpu_colschema *)std::calloc((size_t)std::max(in->ncols, 1), sizeof(tfgpu_colschema));
   std::vector<int> order((size_t)in->ncols);
@@ -198,10 +225,44 @@ int tfgpu_apply(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, tf
   for (int i = 0; i < nplans; i++)  // (judged from the plans alone, before the batch is looked at)
     if (plans[i] && plans[i]->kind == PK_TABLE_SPLITTER)
       return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_apply: table_splitter_transformer files the rows under several tables and a batch is one table: run the chain with tfgpu_apply_split");
+  if (chain_raw_doc(plans, nplans))
+    return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_apply: raw_doc_grouper writes etl_updated_at from the rows' CommitTime, which this entry does not see: run the chain with tfgpu_apply_meta");
   if (!in || !out) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply: null argument");
   std::lock_guard<std::mutex> lk(ctx().mu);
   ApplyCtx ax;
   std::unique_ptr<tfgpu_dbatch> cur = run_chain(plans, nplans, *in, ax);
+  if (nerrs) *nerrs = (int64_t)ax.errs.size();
+  if (errs) for (int64_t k = 0; k < errs_cap && k < (int64_t)ax.errs.size(); k++) errs[k] = ax.errs[(size_t)k];
+  *out = cur.release();
+  return TFGPU_OK;
+  TF_API_END
+}
+
+// tfgpu_apply with the rows' CommitTime in reach (ApplyCtx): the entry a raw_doc_grouper runs through
+int tfgpu_apply_meta(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, const tfgpu_row_meta *meta, tfgpu_dbatch **out, tfgpu_row_error *errs,
+                     int64_t errs_cap, int64_t *nerrs) {
+  TF_API_BEGIN
+  if (nplans > 0 && !plans) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply_meta: null argument");
+  for (int i = 0; i < nplans; i++)
+    if (plans[i] && plans[i]->kind == PK_TABLE_SPLITTER)
+      return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_apply_meta: table_splitter_transformer files the rows under several tables and a batch is one table: run the chain with tfgpu_apply_split");
+  if (!in || !out) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply_meta: null argument");
+  if (meta && meta->n < 0) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply_meta: meta->n is negative");
+  std::lock_guard<std::mutex> lk(ctx().mu);
+  ApplyCtx ax;
+  ax.has_meta = true;
+  Buf staged;  // a host array lives in HBM for the call
+  if (meta && meta->commit_time && meta->n > 0) {
+    ax.meta_n = meta->n;
+    if (meta->mem == TFGPU_MEM_DEVICE) ax.commit_time = meta->commit_time;
+    else {
+      staged = dalloc((size_t)meta->n * 8 + 16);
+      h2d(staged->p, meta->commit_time, (size_t)meta->n * 8);
+      ax.commit_time = ptr<uint64_t>(staged);
+    }
+  } else if (meta && meta->commit_time) ax.meta_n = 0, ax.commit_time = meta->commit_time;  // (an array of no entries: any row that reads it is out of range)
+  std::unique_ptr<tfgpu_dbatch> cur = run_chain(plans, nplans, *in, ax);
+  if (staged) tf::sync();  // (the kernels that read the staged array have run before its block goes back to the pool)
   if (nerrs) *nerrs = (int64_t)ax.errs.size();
   if (errs) for (int64_t k = 0; k < errs_cap && k < (int64_t)ax.errs.size(); k++) errs[k] = ax.errs[(size_t)k];
   *out = cur.release();

@@ -573,7 +573,25 @@ std::unique_ptr<tfgpu_plan> make_plan(const std::string &type_name, const std::s
     p->splitter = cfg.s("splitter");
     if (cfg.flag("useLegacyLf"))
       throw Error(TFGPU_ERR_UNSUPPORTED, "table_splitter_transformer useLegacyLf=true builds the name with generic_parser.TableSplitter and castx.ToStringE on the host; not a device transform");
-  } else if (type_name == "lambda" || type_name == "dbt" || type_name == "logger" || type_name == "yt_dict_transformer" || type_name == "raw_doc_grouper" ||
+  } else if (type_name == "raw_doc_grouper") {  // raw_doc_grouper/raw_doc_grouper.go:39-44, 195-236
+    p->kind = PK_RAW_DOC_GROUPER;
+    p->columns.init({}, {});
+    p->rd_keys = cfg.strings("keys");
+    p->rd_fields = cfg.strings("fields");
+    auto has = [](const std::vector<std::string> &v, const std::string &n) { return std::find(v.begin(), v.end(), n) != v.end(); };
+    for (const char *name : {"etl_updated_at", "doc"})
+      if (!has(p->rd_keys, name) && !has(p->rd_fields, name)) p->rd_fields.push_back(name);
+    for (size_t i = 0; i < p->rd_keys.size(); i++)
+      for (size_t j = 0; j < i; j++)
+        if (p->rd_keys[i] == p->rd_keys[j]) cfg_error("Can't use same keys column names twice: " + join_keys(p->rd_keys));
+    for (auto &k : p->rd_keys)
+      if (has(p->rd_fields, k)) cfg_error("Can't use same column as key and non-key : " + k);
+    try { p->tables = tables_of(cfg); }
+    catch (const Error &e) { if (e.code == TFGPU_ERR_CONFIG) cfg_error(std::string("unable to init table filter: ") + e.what()); throw; }
+    if (cfg.flag("shouldUpdateOldKeys"))
+      throw Error(TFGPU_ERR_UNSUPPORTED, "raw_doc_grouper shouldUpdateOldKeys=true gives every Update row its own OldKeys name list (processUpdateItem appends the additional keys row by "
+                                         "row: ragged OldKeys), which a columnar batch cannot express; not a device transform");
+  } else if (type_name == "lambda" || type_name == "dbt" || type_name == "logger" || type_name == "yt_dict_transformer" ||
              type_name == "raw_cdc_doc_grouper" || type_name == "number_to_float_transformer" ||
              type_name == "problem_item_detector" || type_name == "batch_splitter" || type_name == "filter_strm_access_log" || type_name == "jsonparser" ||
              type_name == "filter_rows_by_ids" || type_name == "mongo_pk_extender") {
@@ -583,6 +601,12 @@ std::unique_ptr<tfgpu_plan> make_plan(const std::string &type_name, const std::s
     throw Error(TFGPU_ERR_UNKNOWN_TYPE, "transformer type not registered: " + type_name);
   }
   return p;
+}
+
+bool rawdoc_special(const std::string &name) { return name == "etl_updated_at" || name == "doc"; }
+const tfgpu_plan *chain_raw_doc(tfgpu_plan *const *plans, int nplans) {
+  for (int i = 0; plans && i < nplans; i++) if (plans[i] && plans[i]->kind == PK_RAW_DOC_GROUPER) return plans[i];
+  return nullptr;
 }
 
 static bool todt_col(const tfgpu_plan &p, const std::string &name, int dtype) {
@@ -639,6 +663,12 @@ bool plan_suitable(const tfgpu_plan &p, const std::string &ns, const std::string
     case PK_SQL:  // clickhouse_local.go:335-349: the table filter decides; a result without columns / key is only warned about
       return p.tables.match_table(ns, name);
     case PK_TABLE_SPLITTER: return p.tables.match_table(ns, name);  // table_splitter.go:96-98
+    case PK_RAW_DOC_GROUPER: {  // raw_doc_grouper.go:115-121: containsAllFields over the schema's names (etl_updated_at / doc need not be there)
+      if (!p.tables.match_table(ns, name)) return false;
+      auto in_schema = [&](const std::string &n) { for (int i = 0; i < s.ncols; i++) if (n == (s.cols[i].name ? s.cols[i].name : "")) return true; return false; };
+      for (auto *list : {&p.rd_keys, &p.rd_fields}) for (auto &n : *list) if (!rawdoc_special(n) && !in_schema(n)) return false;
+      return true;
+    }
     case PK_REGEX_REPLACE: return p.tables.match(name);  // transformer.go:64-66: the table's name alone, no namespace variants
     case PK_TO_DATETIME:  // to_datetime.go:63-76
       if (!p.tables.match_table(ns, name)) return false;
@@ -688,6 +718,7 @@ std::string plan_description(const tfgpu_plan &p) {
     case PK_TABLE_SPLITTER:  // table_splitter.go:104-110: `columns=(...)` is built from the tables' ExcludeRegexp, as the reference builds it
       return "Table splitter for tables=(include: " + trim_and_more(join(p.tables.include_src, "|"), 100) + ", exclude: " + trim_and_more(join(p.tables.exclude_src, "|"), 100) +
              "); columns=(" + trim_and_more(join(p.tables.exclude_src, ","), 100) + "); splitter=" + p.splitter;
+    case PK_RAW_DOC_GROUPER: return "Return item as primary keys " + join(p.rd_keys, ", ") + " and json, containing the rest";  // raw_doc_grouper.go:154-156
     case PK_REPLACE_PK: return "Replace primary keys to: " + join_keys(p.new_keys) + " ";
     case PK_SHARDER:
       if (p.columns.empty()) return "Transform to shard tables by field values";

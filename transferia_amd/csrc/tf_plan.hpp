@@ -58,7 +58,7 @@ std::vector<FTerm> parse_filter(const std::string &src);  // throws Error(TFGPU_
 
 }  // namespace tf
 
-enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL, PK_REGEX_REPLACE, PK_TABLE_SPLITTER };
+enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL, PK_REGEX_REPLACE, PK_TABLE_SPLITTER, PK_RAW_DOC_GROUPER };
 
 namespace tf {
 // ---- `sql` transformer, device subset (tf_sql.cpp) ----------------------------------------------------------------------
@@ -135,6 +135,8 @@ struct tfgpu_plan {
   // table_splitter_transformer (tf_tablesplit.hip)
   std::vector<std::string> split_cols;  // `columns`: names, in config order (a name may repeat)
   std::string splitter;                 // as configured: empty means "/" when a name is built, Description prints it as it is
+  // raw_doc_grouper (tf_rawdoc.hip)
+  std::vector<std::string> rd_keys, rd_fields;  // `keys` as configured; `fields` with etl_updated_at / doc appended where neither list names them (NewRawDocGroupTransformer)
   // replace_primary_key
   std::vector<std::string> new_keys;
   bool is_new_key(const std::string &n) const {
@@ -168,11 +170,18 @@ std::string type_name(int dtype);                                               
 struct ApplyCtx {
   std::vector<tfgpu_row_error> errs;
   int step = 0;
+  // tfgpu_apply_meta: ChangeItem.CommitTime by INPUT row (row r of a batch reads entry src_row[r]), in HBM; null = the Go zero value in every row
+  bool has_meta = false;               // the call came in through tfgpu_apply_meta (raw_doc_grouper runs only there)
+  const uint64_t *commit_time = nullptr;
+  int64_t meta_n = 0;
 };
 std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
 std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch &in);  // the kinds with a unit of their own: tf_mask.hip, tf_sqleval.hip, tf_regex.hip
 std::unique_ptr<tfgpu_dbatch> apply_sql(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
 std::unique_ptr<tfgpu_dbatch> apply_regex_replace(const tfgpu_plan &p, const tfgpu_dbatch &in);
+std::unique_ptr<tfgpu_dbatch> apply_raw_doc(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);  // tf_rawdoc.hip
+bool rawdoc_special(const std::string &name);                                                            // etl_updated_at / doc (rawDocFields)
+const tfgpu_plan *chain_raw_doc(tfgpu_plan *const *plans, int nplans);                                  // the chain's first raw_doc_grouper, or null
 // plans[0 .. nplans) over a snapshot of `in`, the loop of tfgpu_apply (tf_api.hip; the caller holds the lane's mutex): for tfgpu_apply_split (tf_tablesplit.hip)
 std::unique_ptr<tfgpu_dbatch> run_chain(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch &in, ApplyCtx &ax);
 void mask_precheck(const tfgpu_plan &p, const tfgpu_dbatch &in);  // throws what apply_mask would refuse for the whole batch

@@ -426,6 +426,9 @@ int tfgpu_apply_split(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *
     if (plans[i]->kind == PK_TABLE_SPLITTER)
       return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_apply_split: a table_splitter_transformer that is not the chain's last step (or a second one): the transformers behind it go over each "
                                              "table's batch — run them with tfgpu_apply over tfgpu_tablesplit_batch's results");
+  if (chain_raw_doc(plans, nplans))
+    return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_apply_split: raw_doc_grouper writes etl_updated_at from the rows' CommitTime, which this entry does not see: run it with tfgpu_apply_meta "
+                                           "and split its result with tfgpu_table_split");
   if (plans[nplans - 1]->kind != PK_TABLE_SPLITTER) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply_split: the last plan must be the chain's table_splitter_transformer");
   if (!in || !out) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_apply_split: null argument");
   std::lock_guard<std::mutex> lk(ctx().mu);

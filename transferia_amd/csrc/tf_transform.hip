@@ -1,6 +1,6 @@
 // tf_transform.hip — device kernels behind abstract.Transformer.Apply for the
 // row transformers of SURVEY.md §8a (a6–a13), plus the apply dispatcher (mask_field: tf_mask.hip, sql: tf_sqleval.hip,
-// regex_replace_transformer: tf_regex.hip; the row machinery under all of them: tf_rows.hip).
+// regex_replace_transformer: tf_regex.hip; raw_doc_grouper: tf_rawdoc.hip; the row machinery under all of them: tf_rows.hip).
 //
 // All kernels are byte/row kernels: one lane per row, column-major (Arrow)
 // buffers so that neighbouring lanes touch neighbouring addresses.  None of
@@ -695,6 +695,12 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
   // regex_replace_transformer's rule is positional (the i-th value against the i-th schema column): rows that list their own columns stay with the stock path too.
   if (p.kind == PK_TABLE_SPLITTER)
     throw Error(TFGPU_ERR_UNSUPPORTED, "table_splitter_transformer files the rows under several tables and a batch is one table: it runs last, through tfgpu_apply_split");
+  if (p.kind == PK_RAW_DOC_GROUPER) {  // it reads ABSENT cells itself (a row's doc holds the columns the row lists)
+    if (!ax.has_meta)
+      throw Error(TFGPU_ERR_UNSUPPORTED, "raw_doc_grouper writes etl_updated_at from the rows' CommitTime, which this entry does not see: run the chain with tfgpu_apply_meta");
+    if (in.col_order)
+      throw Error(TFGPU_ERR_UNSUPPORTED, "raw_doc_grouper: the batch's rows carry their own ColumnNames order (col_order: a collapsed batch), which the result's column list does not carry");
+  }
   if (p.kind == PK_SQL || p.kind == PK_REGEX_REPLACE || (in.col_order && p.kind != PK_SHARDER)) refuse_absent(in);
   // `in` is the caller's OWN copy of the handle it was given (tfgpu_apply and push_run take it with snapshot(), under the transition's lock): nobody
   // else changes it.  A copy taken after another lane made the handle dense carries that lane's event: this lane's stream waits for it here.
@@ -712,6 +718,7 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
     case PK_REPLACE_PK: return apply_replace_pk(p, in);
     case PK_SQL: return apply_sql(p, in, ax);
     case PK_REGEX_REPLACE: return apply_regex_replace(p, in);
+    case PK_RAW_DOC_GROUPER: return apply_raw_doc(p, in, ax);
     case PK_TABLE_SPLITTER: break;  // (refused above)
   }
   throw Error(TFGPU_ERR_INVALID, "unknown plan kind");

@@ -263,6 +263,9 @@ static void refuse_splitter(const tfgpu_plan *p) {
   if (p->kind == PK_TABLE_SPLITTER)
     throw tf::Error(TFGPU_ERR_UNSUPPORTED, "unable to init: table_splitter_transformer: its rows leave under several tables, which transformation.Push does not hand on yet "
                                            "(tfgpu_apply_split runs it over one batch)");
+  if (p->kind == PK_RAW_DOC_GROUPER)
+    throw tf::Error(TFGPU_ERR_UNSUPPORTED, "unable to init: raw_doc_grouper: etl_updated_at is the rows' CommitTime, and transformation.Push carries no row meta yet "
+                                           "(tfgpu_apply_meta runs the chain over one batch)");
 }
 
 extern "C" {

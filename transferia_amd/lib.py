@@ -34,7 +34,7 @@ EXPORTS = [
     "tfgpu_prof_get", "tfgpu_prof_get_units", "tfgpu_parquet_read_object", "tfgpu_parquet_staging_size", "tfgpu_parquet_read_staged", "tfgpu_parquet_resolve_schema", "tfgpu_dbatch_nrows", "tfgpu_dbatch_dense",
     "tfgpu_nginx_format_compile", "tfgpu_nginx_format_free", "tfgpu_nginx_format_ntokens", "tfgpu_nginx_format_token", "tfgpu_nginx_format_nfields", "tfgpu_nginx_format_field",
     "tfgpu_nginx_resolve_schema", "tfgpu_nginx_options_default", "tfgpu_nginx_parse", "tfgpu_nginx_tile_bytes", "tfgpu_nginx_workgroup_lines",
-    "tfgpu_table_split", "tfgpu_apply_split", "tfgpu_tablesplit_rows", "tfgpu_tablesplit_count", "tfgpu_tablesplit_name", "tfgpu_tablesplit_table_rows",
+    "tfgpu_apply_meta", "tfgpu_table_split", "tfgpu_apply_split", "tfgpu_tablesplit_rows", "tfgpu_tablesplit_count", "tfgpu_tablesplit_name", "tfgpu_tablesplit_table_rows",
     "tfgpu_tablesplit_row_tables", "tfgpu_tablesplit_batch", "tfgpu_tablesplit_free",
 ]
 
@@ -86,6 +86,7 @@ def load():
     L.tfgpu_dbatch_free.argtypes = [P]
     L.tfgpu_dbatch_free.restype = None
     L.tfgpu_apply.argtypes = [C.POINTER(P), C.c_int, P, C.POINTER(P), C.POINTER(abi.CRowError), C.c_int64, C.POINTER(C.c_int64)]
+    L.tfgpu_apply_meta.argtypes = [C.POINTER(P), C.c_int, P, C.POINTER(abi.CRowMeta), C.POINTER(P), C.POINTER(abi.CRowError), C.c_int64, C.POINTER(C.c_int64)]
     L.tfgpu_csv_split_rows.argtypes = [P, C.c_uint64, C.c_int, C.POINTER(P), C.POINTER(C.c_int64)]
     L.tfgpu_transformation_create.argtypes = [C.POINTER(P), C.c_int, C.POINTER(P)]
     L.tfgpu_transformation_destroy.argtypes = [P]
@@ -616,6 +617,31 @@ def apply_chain(transformers: Sequence[Transformer], batch: DeviceBatch, max_err
     errs = _errbuf(max_errors)
     nerr = C.c_int64(0)
     _check(load().tfgpu_apply(arr, n, batch._h, C.byref(out), errs, max_errors, C.byref(nerr)))
+    el = [(int(errs[i].row), abi.ROWERR.get(int(errs[i].code), str(errs[i].code)), int(errs[i].step), int(errs[i].column))
+          for i in range(min(int(nerr.value), max_errors))]
+    return TransformerResult(DeviceBatch(out), el)
+
+
+def apply_meta(transformers: Sequence[Transformer], batch: DeviceBatch, commit_time=None, max_errors: int = 1 << 16) -> TransformerResult:
+    """tfgpu_apply_meta: apply_chain with the rows' CommitTime in reach — the entry a chain holding a raw_doc_grouper runs through.
+    commit_time: None (the Go zero value in every row), uint64 nanoseconds by INPUT row (row r reads entry src_row[r]) as a host sequence
+    or as a DeviceBuffer of 8-byte entries, or a ready abi.CRowMeta."""
+    init()
+    n = len(transformers)
+    arr = (C.c_void_p * max(n, 1))(*[t._h for t in transformers])
+    if commit_time is None:
+        meta = None
+    elif isinstance(commit_time, abi.CRowMeta):
+        meta = commit_time
+    elif isinstance(commit_time, DeviceBuffer):
+        meta = abi.row_meta_device(commit_time.size // 8, commit_time=commit_time.ptr)
+    else:
+        ct = np.ascontiguousarray(commit_time, dtype=np.uint64)
+        meta = abi.row_meta(len(ct), commit_times=ct)
+    out = C.c_void_p()
+    errs = _errbuf(max_errors)
+    nerr = C.c_int64(0)
+    _check(load().tfgpu_apply_meta(arr, n, batch._h, C.byref(meta) if meta is not None else None, C.byref(out), errs, max_errors, C.byref(nerr)))
     el = [(int(errs[i].row), abi.ROWERR.get(int(errs[i].code), str(errs[i].code)), int(errs[i].step), int(errs[i].column))
           for i in range(min(int(nerr.value), max_errors))]
     return TransformerResult(DeviceBatch(out), el)
