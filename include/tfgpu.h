@@ -127,9 +127,16 @@ typedef struct tfgpu_column {
   int32_t dtype;      /* schema DataType looked up BY NAME       */
   int32_t repr;       /* tfgpu_repr                                           */
   void *values;       /* fixed-width reprs: nrows elements; else NULL         */
-  uint32_t *offsets;  /* var-width reprs: nrows+1 offsets into data           */
+  uint32_t *offsets;  /* var-width reprs: nrows+1 non-decreasing offsets, ABSOLUTE
+                         into data: cell i is data[offsets[i] .. offsets[i+1]).
+                         offsets[0] may be non-zero (a slice of a larger buffer,
+                         as Arrow hands one on)                               */
   uint8_t *data;      /* var-width payload                                    */
-  uint64_t data_len;  /* bytes in data                                        */
+  uint64_t data_len;  /* bytes in data, >= offsets[nrows]; it may be MORE (a
+                         capacity): bytes outside [offsets[0], offsets[nrows])
+                         belong to no cell and no entry reads them.  A HOST
+                         upload takes offsets[nrows] itself; a DEVICE upload
+                         copies data_len bytes as stated                      */
   int32_t *nanos;     /* TFGPU_R_TIME only; NULL = all zero                   */
   uint8_t *validity;  /* bitmap, bit i (LSB first) = 1 if value i != nil;
                          NULL = no nil values                                 */
@@ -283,7 +290,11 @@ int tfgpu_lane_device(int lane, int *device);  /* the HIP device lane `lane` liv
  *   tfgpu_dbatch_concat:  the parts' rows, parts in order, on the calling lane.  The parts may live on any lane / device
  *                         (their lanes synchronised by the caller); columns, representations, TableSchema and table id
  *                         must agree.  row_base[g] (optional) is added to part g's src_row (a part without src_row
- *                         counts 0, 1, …), which turns shard-local source rows back into rows of the sharded batch.    */
+ *                         counts 0, 1, …), which turns shard-local source rows back into rows of the sharded batch.
+ *                         The merged batch has a src_row when row_base is given or a part WITH rows has one.  A part's
+ *                         text is bytes [offsets[0], offsets[nrows]) of its data, wherever they lie in it; a text column
+ *                         of a part with rows that has no offsets, or offsets that run backwards or past data_len, is
+ *                         refused (TFGPU_ERR_INVALID).                                                               */
 int tfgpu_dbatch_slice(const tfgpu_dbatch *b, int64_t row0, int64_t nrows, tfgpu_dbatch **out);
 int tfgpu_dbatch_to_lane(const tfgpu_dbatch *b, int lane, tfgpu_dbatch **out);
 int tfgpu_shard_rows(const tfgpu_dbatch *b, int nshards, const int *lanes, tfgpu_dbatch **out, int64_t *row0);

@@ -214,14 +214,51 @@ static std::unique_ptr<tfgpu_dbatch> concat(const std::vector<const tfgpu_dbatch
     }
     return out;
   };
+  // A part's text is what ITS offsets name: bytes [offsets[0], offsets[nrows]) of its payload.  Neither end is promised to be 0 / data_len
+  // (include/tfgpu.h: an upload of an Arrow-style slice starts past 0, a device upload may state a capacity), so both ends of every text
+  // column of every part with rows come to the host: ONE gather and ONE read-back for all of them, as slice_many does for its cut points.
+  std::vector<int> var_slot(p0.cols.size() + p0.old_keys.size(), -1);  // [column, OldKeys columns behind them]: which text column it is, or -1
+  size_t nvar_cols = 0;
+  for (size_t i = 0; i < var_slot.size(); i++) if (repr_is_var((i < p0.cols.size() ? p0.cols[i] : p0.old_keys[i - p0.cols.size()]).repr)) var_slot[i] = (int)nvar_cols++;
+  auto slot_of = [&](size_t i, bool old) { return (size_t)var_slot[old ? p0.cols.size() + i : i]; };
+  std::vector<Buf> var_off(nvar_cols * parts.size());     // [text column][part]: the part's offsets on this device (staged when remote), null for a part without rows
+  std::vector<uint32_t> var_end(var_off.size() * 2, 0u);  // [text column][part]{first, last offset}
+  if (nvar_cols && n > 0) {
+    std::vector<const uint32_t *> arrays; std::vector<int64_t> idx; std::vector<size_t> slot;
+    auto note = [&](size_t i, bool old) {
+      const size_t v = slot_of(i, old);
+      for (size_t g = 0; g < parts.size(); g++) {
+        const DColumn &c = old ? parts[g]->old_keys[i] : parts[g]->cols[i];
+        const int64_t k = parts[g]->nrows;
+        if (!k) continue;
+        if (!c.offsets) throw Error(TFGPU_ERR_INVALID, "tfgpu_dbatch_concat: column " + c.name + " of a part holds no offsets");
+        Buf off = local(c.offsets, (size_t)(k + 1) * 4);
+        var_off[v * parts.size() + g] = off;
+        for (int64_t at : {(int64_t)0, k}) { arrays.push_back(ptr<uint32_t>(off)); idx.push_back(at); slot.push_back((v * parts.size() + g) * 2 + (at ? 1 : 0)); }
+      }
+    };
+    for (size_t i = 0; i < p0.cols.size(); i++) if (repr_is_var(p0.cols[i].repr)) note(i, false);
+    for (size_t i = 0; i < p0.old_keys.size(); i++) if (repr_is_var(p0.old_keys[i].repr)) note(i, true);
+    Buf da = upload_small(arrays.data(), arrays.size() * sizeof(void *)), di = upload_small(idx.data(), idx.size() * 8), out = dalloc(arrays.size() * 4);
+    shard_gather_u32<<<blocks_of((int64_t)arrays.size()), 256, 0, st>>>(reinterpret_cast<const uint32_t *const *>(da->p), ptr<int64_t>(di), (int64_t)arrays.size(), ptr<uint32_t>(out));
+    std::vector<uint32_t> h(arrays.size());
+    d2h(h.data(), out->p, h.size() * 4);
+    tf::sync();
+    for (size_t j = 0; j < h.size(); j++) var_end[slot[j]] = h[j];
+  }
   auto col = [&](size_t i, bool old) {
     auto of = [&](const tfgpu_dbatch &p) -> const DColumn & { return old ? p.old_keys[i] : p.cols[i]; };
     const DColumn &c0 = of(p0);
     DColumn d;
     d.name = c0.name; d.dtype = c0.dtype; d.repr = c0.repr;
     if (repr_is_var(c0.repr)) {
+      const size_t v = slot_of(i, old);
       uint64_t total = 0;
-      for (auto *p : parts) total += of(*p).data_len;
+      for (size_t g = 0; g < parts.size(); g++) {
+        const uint32_t lo = var_end[(v * parts.size() + g) * 2], hi = var_end[(v * parts.size() + g) * 2 + 1];
+        if (hi < lo || hi > of(*parts[g]).data_len) throw Error(TFGPU_ERR_INVALID, "tfgpu_dbatch_concat: column " + c0.name + " of a part holds offsets outside its data");
+        total += hi - lo;
+      }
       if (total >> 32) throw Error(TFGPU_ERR_UNSUPPORTED, "tfgpu_dbatch_concat: column " + c0.name + " exceeds 4 GiB of text");
       d.data_len = total;
       d.data = dalloc((size_t)total);
@@ -230,11 +267,14 @@ static std::unique_ptr<tfgpu_dbatch> concat(const std::vector<const tfgpu_dbatch
       for (size_t g = 0; g < parts.size(); g++) {
         const DColumn &c = of(*parts[g]);
         const int64_t k = parts[g]->nrows;
-        xcopy((char *)d.data->p + at, c.payload() ? c.payload()->p : nullptr, (size_t)c.data_len);
-        // the part's offsets, shifted, straight into place (its last entry is overwritten by the next part's first: same value)
-        Buf off = local(c.offsets, (size_t)(k + 1) * 4);
-        if (off) shard_rebase_offsets<<<blocks_of(k + 1), 256, 0, st>>>(ptr<uint32_t>(off), k + 1, 0u, (uint32_t)at, ptr<uint32_t>(d.offsets) + base[g]);
-        at += c.data_len;
+        const Buf &off = var_off[v * parts.size() + g];
+        if (!off) continue;  // (a part without rows brings no text and no offset)
+        const uint32_t lo = var_end[(v * parts.size() + g) * 2], hi = var_end[(v * parts.size() + g) * 2 + 1];
+        if (hi > lo) xcopy((char *)d.data->p + at, ptr<uint8_t>(c.payload()) + lo, (size_t)(hi - lo));
+        // the part's offsets, rebased from its own first one, straight into place: its last entry lands where the next part's first will, and
+        // both are the write position there (this part's first + the bytes it brought)
+        shard_rebase_offsets<<<blocks_of(k + 1), 256, 0, st>>>(ptr<uint32_t>(off), k + 1, lo, (uint32_t)at, ptr<uint32_t>(d.offsets) + base[g]);
+        at += hi - lo;
       }
       if (n == 0) TF_HIP(hipMemsetAsync(d.offsets->p, 0, 4, st));
     } else {
@@ -261,7 +301,9 @@ static std::unique_ptr<tfgpu_dbatch> concat(const std::vector<const tfgpu_dbatch
   for (size_t i = 0; i < p0.cols.size(); i++) r->cols.push_back(col(i, false));
   for (size_t i = 0; i < p0.old_keys.size(); i++) r->old_keys.push_back(col(i, true));
   bool anyp = false, anyk = false, anys = false, anyid = false;
-  for (auto *p : parts) { anyp = anyp || (bool)p->old_present; anyk = anyk || (bool)p->kind; anys = anys || (bool)p->src_row; anyid = anyid || (bool)p->part_id; }
+  // (src_row: only a part with rows decides — a zero-row slice of a filtered batch still "has" one, and must not turn the other parts' identity into
+  // per-part row numbers that collide)
+  for (auto *p : parts) { anyp = anyp || (bool)p->old_present; anyk = anyk || (bool)p->kind; anys = anys || (p->nrows && p->src_row); anyid = anyid || (bool)p->part_id; }
   if (!p0.old_keys.empty()) r->old_present = bitmap([&](const tfgpu_dbatch &p) -> const Buf & { return p.old_present; }, anyp);
   if (anyk) {
     r->kind = dalloc((size_t)n);
