@@ -186,10 +186,17 @@ inline size_t repr_width(int r) {
   }
 }
 
-// Late-materialised text cells (CSV ingest): until a consumer needs the packed Arrow payload, a text column is its
-// offsets (lengths already scanned, data_len known) plus, per row, where the cell sits in the SOURCE text — the columnar
-// form of Go substrings that alias the chunk they were cut from.  Row compaction packs the kept cells straight from
-// the source; everything else calls materialize() first.  `packed` is shared by every copy of the column.
+// Late-materialised text cells (CSV ingest): until a consumer needs the packed Arrow payload, a text column is, per row,
+// its length and where the cell sits in the SOURCE text — the columnar form of Go substrings that alias the chunk they were
+// cut from.  A column has three states:
+//   lengths   view->lens set, DColumn::offsets null, data_len not meaningful: nobody has asked for offsets yet (the tile
+//             parser and a gather of such a column leave it so: a row filter in front of a sink that drops the batch, or
+//             gathers it again, never pays for a scan);
+//   offsets   DColumn::offsets / data_len set, no payload yet (lazy());
+//   packed    view->packed (or DColumn::data) holds the Arrow payload.
+// Row compaction gathers lengths and positions; everything else calls materialize() first, the single gate that scans the
+// lengths (out of place: `lens` is never written after the parse) and packs.  `offsets`, `total` and `packed` are shared by
+// every copy of the column.
 struct TextView {
   Buf src;              // the CSV text, kept alive here
   Buf fstart;           // u32[nrows]: offset of the cell in src | bit 31: collapse doubled quotes; low 31 bits all ones: DefaultValue
@@ -197,6 +204,9 @@ struct TextView {
   bool jsonnum = false; // DefaultValue of a double is json.Number("0")
   bool has_special = true;  // some cell is not a plain byte range of src (doubled quotes, DefaultValue text)
   Buf packed;           // set once by materialize()
+  Buf lens;             // u32[nrows]: the cells' lengths, or null (a column born with offsets); never written after the parse / gather that made it
+  Buf offsets;          // set once by materialize() (ensure_text_offsets): the exclusive scan of lens, nrows + 1 entries
+  uint64_t total = 0;   // set once with offsets: offsets[nrows]
 };
 struct DColumn {
   std::string name;
@@ -208,9 +218,13 @@ struct DColumn {
   std::shared_ptr<TextView> view;  // non-null while `data` may still be unpacked
   const Buf &payload() const { return (!data && view) ? view->packed : data; }
   bool lazy() const { return !data && view && !view->packed; }
+  bool lens_only() const { return view && view->lens && !offsets; }  // the lengths state: offsets and data_len are not there yet
 };
 // Packs the lazy text columns of `b` (all of them, or only those listed) from their source text; no-op otherwise.
 void materialize(const struct ::tfgpu_dbatch &b, const std::vector<const DColumn *> *only = nullptr);
+// The head of materialize(): every column of `b` still in the lengths state gets offsets and data_len — one out-of-place segmented
+// scan, one read-back of the totals and one sync for the views nobody has scanned yet, none for views a sharing handle scanned (tf_rows.hip).
+void ensure_text_offsets(const struct ::tfgpu_dbatch &b);
 // Gathers the rows of a batch whose rows are still a selection (tfgpu_dbatch::pending); no-op otherwise.  dense() takes the lane's
 // mutex itself (call it BEFORE locking); dense_locked() is for callers that hold it.
 // dense() also REFUSES (TFGPU_ERR_UNSUPPORTED, by name) a batch that holds ABSENT cells (DColumn::absent) unless the caller says it
@@ -279,6 +293,8 @@ void exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, bool with_
 // Segmented variant for `nseg` equally-long arrays laid out back to back
 // (used for the string columns of a batch): each segment scanned on its own.
 void exclusive_scan_u32_segments(uint32_t *inout, int64_t seg_len, int nseg, int64_t seg_stride);
+// the same out of place: `in` is left as it is (segments seg_stride apart in both arrays)
+void exclusive_scan_u32_segments(const uint32_t *in, uint32_t *out, int64_t seg_len, int nseg, int64_t seg_stride);
 // keep flags (0 / 1) → sel[k] = the k-th i with keep[i] != 0, *count = how many (a device word), in two launches that never store
 // the scan.  false, and nothing enqueued: n == 0 or above 4 Mi — scan and build the selection from the scan.
 bool select_kept_u32(const uint32_t *keep, int64_t n, int32_t *sel, uint32_t *count);

@@ -1936,7 +1936,7 @@ __global__ void csv_collect(const uint32_t *nerr, const uint32_t *last, const ui
     if (i == 1) out[1] = le;
   } else if (i == 1) out[1] = *last;
   if (i == 0) out[0] = *nerr;
-  for (int s = i; s < nstr; s += blockDim.x) { out[2 + s] = lens_all[(int64_t)s * seg_stride + nrows]; out[2 + nstr + s] = fstart_all[(int64_t)s * fstride + FS_HDR - 1]; }
+  for (int s = i; s < nstr; s += blockDim.x) { out[2 + s] = lens_all ? lens_all[(int64_t)s * seg_stride + nrows] : 0u; out[2 + nstr + s] = fstart_all[(int64_t)s * fstride + FS_HDR - 1]; }  // (lens_all null: the lengths stay unscanned, there are no totals)
 }
 // everything the parse kernels count into, in one launch: the text columns' flag words, the two hand-over lists' counters (and the
 // consumed offset behind the first), the error count, the sized-ahead form's overflow word
@@ -2084,6 +2084,13 @@ static void materialize_cols(const tfgpu_dbatch &b, const std::vector<const DCol
   const int64_t nrows = b.nrows;
   struct Grp { const uint8_t *src; uint8_t quote; std::vector<CopyCol> all, lng, sht; };
   std::vector<Grp> groups;  // by source text (one, in practice)
+  {  // a column about to be read that is still in the lengths state: offsets and data_len first (all such columns of the batch at once)
+    bool need = false;
+    auto look = [&](const DColumn &d) { if (d.lens_only() && !(only && std::find(only->begin(), only->end(), &d) == only->end())) need = true; };
+    for (auto &d : b.cols) look(d);
+    for (auto &d : b.old_keys) look(d);
+    if (need) ensure_text_offsets(b);
+  }
   auto visit = [&](const DColumn &d) {
     if (!d.lazy()) return;
     if (only && std::find(only->begin(), only->end(), &d) == only->end()) return;
@@ -2610,7 +2617,18 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     { KernelTimer t("csv_parse_tiles_general"); csv_parse_tiles_general<<<(unsigned)std::min<int64_t>(ntiles + rtiles, 2048), CT_THREADS, 0, st>>>(pp); }
     { KernelTimer t("csv_parse_listed"); csv_parse_listed<<<(unsigned)std::min<int64_t>(blocks_for(slow_cap, 64), 1024), 64, 0, st>>>(pp); }
   }
-  if (nrows && nstr) {
+  // ---- text lengths: the tile path leaves them UNSCANNED (TextView::lens) — offsets are made when, and if, a reader asks for them
+  //      (materialize() → ensure_text_offsets): a row filter in front of a sink that drops the batch or gathers the kept rows never
+  //      reads them, and gather_batch wants the lengths back anyway.  Nobody reads a failed line's lengths then (compact_rows below
+  //      gathers the kept rows' only), nor the slots beyond the true count of the sized-ahead form (nrows is corrected before the
+  //      views are made): csv_zero_err_lens goes with the scan.  The per-row path, TFGPU_CSV_EAGER=1 and text in a foreign buffer
+  //      pack at once and scan here; TFGPU_CSV_SCAN_EAGER=1 scans here whatever the path (A/B runs, the cross-check form). ----
+  Buf src_block = staged ? staged : find_device_block(data);  // a foreign device pointer cannot be kept alive: pack now
+  static const bool force_eager = [] { const char *e = std::getenv("TFGPU_CSV_EAGER"); return e && e[0] == '1'; }();
+  static const bool scan_eager = [] { const char *e = std::getenv("TFGPU_CSV_SCAN_EAGER"); return e && e[0] == '1'; }();
+  const bool lens_state = !rowpath && src_block && !force_eager && !scan_eager;
+  if (lens_state) {  // (nothing to launch)
+  } else if (nrows && nstr) {
     csv_zero_err_lens<<<blocks_for(nrows, 256), 256, 0, st>>>(ptr<uint8_t>(err), nrows, ptr<CsvCol>(bcols), ncols, ahead ? ptr<uint32_t>(tile_counts) + ngran : nullptr, skip);
     exclusive_scan_u32_segments(ptr<uint32_t>(lens_all), nrows, nstr, seg_stride);
   } else if (nstr) {
@@ -2618,7 +2636,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   }
   // ---- one read-back: error count, consumed offset, string totals ----
   Buf summary = dalloc((size_t)(2 * nstr + 4) * 4);
-  csv_collect<<<1, 64, 0, st>>>(ptr<uint32_t>(nerr), rowpath ? ptr<uint32_t>(row_start) + nlines : pp.last_end, ptr<uint32_t>(lens_all),
+  csv_collect<<<1, 64, 0, st>>>(ptr<uint32_t>(nerr), rowpath ? ptr<uint32_t>(row_start) + nlines : pp.last_end, lens_state ? nullptr : ptr<uint32_t>(lens_all),
                                 seg_stride, nrows, nstr, ptr<uint32_t>(fstart_all), fstride, ptr<uint32_t>(summary), pp.spec, rtiles, skip,
                                 ptr<uint32_t>(tile_counts) + (spec ? 0 : ngran), pp.ovf);
   const uint32_t *hsum = d2h_u32(summary->p, (size_t)(2 * nstr) + 4);
@@ -2645,21 +2663,22 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     std::fprintf(stderr, "tfgpu csv: %s, %lld tiles of %u KiB, %u general pieces; %u lines, %u per-row\n", use_lanes ? "lanes" : "regular", (long long)(use_lanes ? ltiles : rtiles), (use_lanes ? cl_tile(pp.tile_cpt) : tile_bytes) / 1024u, g, nlines, sl);
   }
 
-  // ---- string payloads: offsets are views into the scanned lens array.  The tile path leaves the cells where they
-  //      are: a text column is (offsets, where each cell sits in the source text) until someone needs it packed
-  //      (materialize(), below) — row compaction packs the kept cells straight from the text. ----
-  Buf src_block = staged ? staged : find_device_block(data);  // a foreign device pointer cannot be kept alive: pack now
-  static const bool force_eager = [] { const char *e = std::getenv("TFGPU_CSV_EAGER"); return e && e[0] == '1'; }();
+  // ---- string payloads: offsets are views into the scanned lens array, or (lens_state) not there yet.  The tile path leaves the
+  //      cells where they are: a text column is (lengths or offsets, where each cell sits in the source text) until someone needs it
+  //      packed (materialize(), below) — row compaction gathers the kept cells' lengths and positions. ----
   for (int s = 0; s < nstr; s++) {
     DColumn &d = db->cols[(size_t)str_col_index[(size_t)s]];
-    d.data_len = hsum[2 + s];
-    d.offsets = subbuf(lens_all, (size_t)s * (size_t)seg_stride * 4, (size_t)(nrows + 1) * 4);
+    if (!lens_state) {
+      d.data_len = hsum[2 + s];
+      d.offsets = subbuf(lens_all, (size_t)s * (size_t)seg_stride * 4, (size_t)(nrows + 1) * 4);
+    }
     if (rowpath) continue;
     auto v = std::make_shared<TextView>();
     v->src = src_block ? src_block : nullptr;
     v->fstart = subbuf(fstart_all, ((size_t)s * (size_t)fstride + FS_HDR) * 4, (size_t)std::max<int64_t>(nrows, 1) * 4);
     v->has_special = hsum[2 + nstr + s] != 0;
     v->quote = opts->quote_char; v->jsonnum = d.repr == TFGPU_R_JSONNUM;
+    if (lens_state) v->lens = subbuf(lens_all, (size_t)s * (size_t)seg_stride * 4, (size_t)nrows * 4);
     d.view = std::move(v);
   }
   if (nstr && rowpath) {

@@ -19,7 +19,7 @@ static inline DCol dcol_of(const DColumn &c) {
   DCol d;
   d.values = c.values ? c.values->p : nullptr;
   d.offsets = ptr<uint32_t>(c.offsets);
-  if (c.lazy()) throw Error(TFGPU_ERR_INVALID, "internal: text column " + c.name + " read before materialize()");
+  if (c.lazy() || c.lens_only()) throw Error(TFGPU_ERR_INVALID, "internal: text column " + c.name + " read before materialize()");
   d.data = ptr<uint8_t>(c.payload());
   d.nanos = ptr<int32_t>(c.nanos);
   d.validity = ptr<uint8_t>(c.validity);

@@ -159,8 +159,6 @@ void mask_precheck(const tfgpu_plan &p, const tfgpu_dbatch &in) {  // (`in`: the
 
 // `in`: a batch nobody else changes meanwhile (apply_plan)
 std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch &in) {
-  auto out = shallow_copy(in);
-  for (auto &sc : out->schema) if (p.mask_has(sc.first)) sc.second = TFGPU_T_UTF8;  // hmac_hasher.go:35-46
   hipStream_t st = ctx().stream;
   // The batch's rows may still be a selection over the batch a filter_rows read (tfgpu_dbatch::pending): the hash reads the masked
   // column's kept rows THROUGH the selection and its 64-byte digests are the first column of the result that exists densely —
@@ -169,6 +167,8 @@ std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch
   const int32_t *sel = in.pending ? ptr<int32_t>(in.pending->sel) : nullptr;
   auto replaced_at = [&](const std::string &name) -> int { for (size_t i = 0; i < in.replaced.size(); i++) if (in.replaced[i].name == name) return (int)i; return -1; };
   materialize_where(from, [&](const DColumn &c) { return p.mask_has(c.name) && replaced_at(c.name) < 0; });
+  auto out = shallow_copy(in);  // (behind materialize: a text column's offsets may have been made just now, and the copy's columns are read below)
+  for (auto &sc : out->schema) if (p.mask_has(sc.first)) sc.second = TFGPU_T_UTF8;  // hmac_hasher.go:35-46
   const int64_t n = in.nrows;
   auto mask_one = [&](const DColumn &c, const int32_t *through) {
     require_serializable(c, "mask_field");

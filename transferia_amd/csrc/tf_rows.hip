@@ -139,10 +139,20 @@ static std::unique_ptr<tfgpu_dbatch> gather_batch(const tfgpu_dbatch &in, const 
   auto col_at = [&](size_t i) -> const DColumn & { return i < ncur ? in.cols[i] : in.old_keys[i - ncur]; };
   out->cols.reserve(ncur); out->old_keys.reserve(in.old_keys.size());
   out->key_names = in.key_names;
-  int nvar = 0;
-  for (size_t i = 0; i < nall; i++) if (repr_is_var(col_at(i).repr) && !(skip && i < ncur && [&] { for (auto &r : *skip) if (r.name == in.cols[i].name) return true; return false; }())) nvar++;
+  {  // packing kept cells now (TFGPU_CSV_EAGER=1), or a payload another handle packed already, is read through the source's offsets
+    bool need = false;
+    for (size_t i = 0; i < nall; i++) if (col_at(i).lens_only() && (eager_text || !col_at(i).lazy())) need = true;
+    if (need) ensure_text_offsets(in);
+  }
+  // a lazy text column still in the lengths state (TextView::lens) leaves in that state: its kept rows' lengths are gathered like any
+  // 4-byte array, nothing is scanned and nothing is read back for it
+  auto stays_lens = [&](const DColumn &c) { return c.lens_only() && c.lazy() && !eager_text; };
+  int nvar = 0, nlens = 0;
+  for (size_t i = 0; i < nall; i++) if (repr_is_var(col_at(i).repr) && !(skip && i < ncur && [&] { for (auto &r : *skip) if (r.name == in.cols[i].name) return true; return false; }())) (stays_lens(col_at(i)) ? nlens : nvar)++;
   const int64_t seg_stride = ((m + 1 + 3) / 4) * 4;
   Buf lens_all = nvar ? dalloc((size_t)nvar * (size_t)seg_stride * 4 + 16) : nullptr;
+  Buf lens_kept = nlens ? dalloc((size_t)nlens * (size_t)seg_stride * 4 + 16) : nullptr;  // the layout of lens_all: ensure_text_offsets scans these segments in one launch
+  size_t li = 0;
   auto skipped = [&](size_t ai) -> const DColumn * {
     if (!skip || ai >= ncur) return nullptr;
     for (auto &r : *skip) if (r.name == in.cols[ai].name) return &r;
@@ -153,7 +163,17 @@ static std::unique_ptr<tfgpu_dbatch> gather_batch(const tfgpu_dbatch &in, const 
     if (const DColumn *have = skipped(ai)) { out->cols.push_back(*have); continue; }
     DColumn o;
     o.name = c.name; o.dtype = c.dtype; o.repr = c.repr;
-    if (repr_is_var(c.repr)) {
+    if (repr_is_var(c.repr) && stays_lens(c)) {
+      if (!c.view->src) throw Error(TFGPU_ERR_INVALID, "internal: text column " + c.name + " lost its source text");
+      auto v = std::make_shared<TextView>();
+      v->src = c.view->src; v->fstart = dalloc((size_t)std::max<int64_t>(m, 1) * 4);
+      v->has_special = c.view->has_special; v->quote = c.view->quote; v->jsonnum = c.view->jsonnum;
+      v->lens = subbuf(lens_kept, li++ * (size_t)seg_stride * 4, (size_t)m * 4);
+      fx.push_back(GFix{c.view->fstart->p, v->fstart->p, 4, 0});
+      fx.push_back(GFix{c.view->lens->p, v->lens->p, 4, 0});
+      o.view = std::move(v);
+    } else if (repr_is_var(c.repr)) {
+      if (c.lens_only()) throw Error(TFGPU_ERR_INVALID, "internal: text column " + c.name + " gathered before its lengths were scanned");
       size_t si = vr.size();
       o.offsets = subbuf(lens_all, si * (size_t)seg_stride * 4, (size_t)(m + 1) * 4);
       if (!c.lazy() || eager_text) o.data = dalloc(c.data_len + 8);  // the source size bounds the kept payload; exact length read back below
@@ -228,6 +248,61 @@ static std::unique_ptr<tfgpu_dbatch> gather_batch(const tfgpu_dbatch &in, const 
     for (int i = 0; i < nvar; i++) out_at(var_cols[(size_t)i]).data_len = h[i];
   }
   return out;
+}
+
+// Lengths → offsets for the text columns of `b` nobody has asked offsets of yet (DColumn::lens_only): the views without offsets are
+// scanned OUT OF PLACE into a new buffer — copies of the column and a PendingRows::src share the view, and another lane may be gathering
+// from `lens` meanwhile — with one launch per run of equally spaced segments (the parser's and gather_batch's layouts are one run), the
+// totals come back in one read-back behind one sync, and the view is published; then the batch's own columns take offsets and data_len
+// from their views (the handle's observable value does not change, as in dense_locked).  A handle that shares a scanned view only
+// copies the two fields.  The publication is under a lock of its own; the scan is complete (synchronised) before it is published.
+static std::mutex g_text_mu;
+void ensure_text_offsets(const tfgpu_dbatch &b) {
+  std::vector<DColumn *> cols;
+  for (auto &c : b.cols) if (c.lens_only()) cols.push_back(const_cast<DColumn *>(&c));
+  for (auto &c : b.old_keys) if (c.lens_only()) cols.push_back(const_cast<DColumn *>(&c));
+  if (cols.empty()) return;
+  std::lock_guard<std::mutex> tl(g_text_mu);
+  const int64_t n = b.nrows;
+  std::vector<TextView *> todo;
+  for (auto *c : cols) {
+    TextView *v = c->view.get();
+    if ((int64_t)(v->lens->bytes / 4) != n) throw Error(TFGPU_ERR_INVALID, "internal: text column " + c->name + " holds lengths of another row count");
+    if (!v->offsets && std::find(todo.begin(), todo.end(), v) == todo.end()) todo.push_back(v);
+  }
+  if (!todo.empty() && n == 0) {
+    for (auto *v : todo) { v->total = 0; v->offsets = dalloc_zero(16); }
+  } else if (!todo.empty()) {
+    std::sort(todo.begin(), todo.end(), [](const TextView *x, const TextView *y) { return x->lens->p < y->lens->p; });
+    struct Run { size_t first; int nseg; int64_t stride; Buf out; const uint32_t *tot; };
+    std::vector<Run> runs;
+    const int64_t own_stride = ((n + 1 + 3) / 4) * 4;
+    for (size_t i = 0; i < todo.size();) {
+      Run r{i, 1, own_stride, nullptr, nullptr};
+      if (i + 1 < todo.size()) {
+        const int64_t d = ptr<uint32_t>(todo[i + 1]->lens) - ptr<uint32_t>(todo[i]->lens);
+        if (d >= n + 1 && d % 4 == 0 && d <= 2 * own_stride + 64) {  // (a far-away neighbour would only size the output for the gap)
+          r.stride = d;
+          while (r.first + (size_t)r.nseg < todo.size() && ptr<uint32_t>(todo[r.first + (size_t)r.nseg]->lens) - ptr<uint32_t>(todo[r.first + (size_t)r.nseg - 1]->lens) == d) r.nseg++;
+        }
+      }
+      i += (size_t)r.nseg;
+      runs.push_back(r);
+    }
+    for (auto &r : runs) {
+      r.out = dalloc((size_t)r.nseg * (size_t)r.stride * 4 + 16);
+      exclusive_scan_u32_segments(ptr<uint32_t>(todo[r.first]->lens), ptr<uint32_t>(r.out), n, r.nseg, r.stride);
+      r.tot = segment_totals_to_host(ptr<uint32_t>(r.out), n, r.nseg, r.stride);
+    }
+    sync();
+    for (auto &r : runs)
+      for (int s = 0; s < r.nseg; s++) {
+        TextView *v = todo[r.first + (size_t)s];
+        v->total = r.tot[s];
+        v->offsets = subbuf(r.out, (size_t)s * (size_t)r.stride * 4, (size_t)(n + 1) * 4);
+      }
+  }
+  for (auto *c : cols) { c->data_len = c->view->total; c->offsets = c->view->offsets; }
 }
 
 std::unique_ptr<tfgpu_dbatch> gather_rows(const tfgpu_dbatch &in, const Buf &sel, int64_t m) { return gather_batch(in, sel, m); }

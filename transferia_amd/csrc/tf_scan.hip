@@ -190,5 +190,10 @@ void exclusive_scan_u32_segments(uint32_t *inout, int64_t seg_len, int nseg, int
   KernelTimer t("scan_u32_segments");
   scan_impl(inout, inout, seg_len, seg_stride, nseg, true);
 }
+void exclusive_scan_u32_segments(const uint32_t *in, uint32_t *out, int64_t seg_len, int nseg, int64_t seg_stride) {
+  if (nseg <= 0) return;
+  KernelTimer t("scan_u32_segments");
+  scan_impl(in, out, seg_len, seg_stride, nseg, true);
+}
 
 }  // namespace tf

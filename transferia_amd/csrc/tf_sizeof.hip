@@ -99,6 +99,7 @@ __global__ void __launch_bounds__(256) deepsizeof_rows(const SzCol *cols, int nc
       if (k.validity && !((k.validity[r >> 3] >> (r & 7)) & 1)) continue;
       s += k.fixed;
       if (k.var == 1) s += k.offsets[r + 1] - k.offsets[r];
+      else if (k.var == 3) s += k.offsets[r];  // a text column still in the lengths state: `offsets` is its lengths (nothing is scanned for a size)
       else if (k.var == 2) {
         bool over = false;
         s += json_deepsize(k.data + k.offsets[r], k.offsets[r + 1] - k.offsets[r], flags & 1u, &over);
@@ -156,6 +157,7 @@ extern "C" int tfgpu_dbatch_deepsizeof(const tfgpu_dbatch *in, uint32_t flags, u
         k.fixed = (uint32_t)repr_width(d.repr);
         if (!k.fixed) return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_dbatch_deepsizeof: column " + d.name + " has no Go value form");
     }
+    if (k.var == 1 && d.lens_only()) { k.var = 3; k.offsets = ptr<uint32_t>(d.view->lens); }
   }
   KernelTimer t("deepsizeof_rows");
   Buf dcols = upload_small(h.data(), h.size() * sizeof(SzCol));

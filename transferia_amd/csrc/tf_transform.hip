@@ -305,7 +305,7 @@ std::unique_ptr<tfgpu_dbatch> run_filter(const std::vector<FExpr> &p_exprs, bool
   }
   std::vector<DCol> cols;
   for (auto &c : in.cols) {
-    if (c.lazy()) { DColumn shell = c; shell.view = nullptr; cols.push_back(dcol_of(shell)); }  // no term reads it: its payload stays unpacked
+    if (c.lazy() || c.lens_only()) { DColumn shell = c; shell.view = nullptr; cols.push_back(dcol_of(shell)); }  // no term reads it: its payload stays unpacked, its lengths unscanned
     else cols.push_back(dcol_of(c));
   }
   auto up = [&](const void *src, size_t bytes) { return upload_const(src, bytes); };  // tables the kernels only read
