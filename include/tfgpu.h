@@ -1306,6 +1306,80 @@ typedef struct tfgpu_dbz_emit_options {
 int tfgpu_debezium_emit(const tfgpu_dbz_emit_options *opts, const tfgpu_dbatch *b, const tfgpu_row_meta *meta, tfgpu_dbuf **keys, uint64_t *key_start,
                         tfgpu_dbuf **values, uint64_t *val_start, uint8_t *val_null, int64_t *msg_row, int64_t cap, int64_t *nmsg);
 
+/* ---- raw_to_table ingest (pkg/parsers/registry/raw_to_table, pkg/util/raw_to_table_common, pkg/util/dlq_maker/queue_dlq_maker) ----------------
+ * A Kafka / YDS topic lands as a table of  topic, partition, offset[, timestamp][, headers][, key], value  rows; a message whose key / value does
+ * not fit the configured type goes to a dead-letter table instead (always timestamp, headers, key and value — both as bytes — plus failure_reason).
+ *
+ * parsers.MessageBatch with keys and headers (tfgpu_messages carries values only).  `mem` says where EVERY array of the batch lives, the index
+ * arrays and bitmaps included.  Nil and empty differ (a nil []byte passes every type check and is a nil cell; an empty non-nil JSON value is
+ * invalid): bit m of value_nil / key_nil / headers_nil (LSB first) = message m's Value / Key / Headers is nil; a NULL bitmap = none is.
+ * key_start NULL = no message has a key (all nil).  Headers are a flattened pair list: message m owns pairs header_pair_start[m] ..
+ * header_pair_start[m+1], a pair names its key and value bytes inside header_bytes.  The pairs of one message may come in any order (a Go map has
+ * none); where a key repeats, the later pair stands.  header_pair_start NULL = every Headers map is nil.                                        */
+typedef struct tfgpu_header_pair { uint32_t key_off, key_len, val_off, val_len; } tfgpu_header_pair;
+typedef struct tfgpu_message_batch {
+  const char *topic;               /* MessageBatch.Topic                                                   */
+  uint32_t partition;              /* MessageBatch.Partition                                               */
+  int32_t mem;                     /* TFGPU_MEM_HOST / TFGPU_MEM_DEVICE                                    */
+  int64_t nmsg;
+  const void *values;              /* Messages[i].Value concatenated                                       */
+  uint64_t values_len;
+  const uint64_t *value_start;     /* [nmsg+1], value_start[nmsg] <= values_len                            */
+  const void *keys;                /* Messages[i].Key concatenated                                         */
+  uint64_t keys_len;
+  const uint64_t *key_start;       /* [nmsg+1] or NULL                                                     */
+  const uint64_t *offset;          /* Message.Offset; NULL = 0                                             */
+  const int64_t *write_time_ns;    /* Message.WriteTime.UnixNano(); NULL = 0                               */
+  const uint8_t *value_nil, *key_nil, *headers_nil;
+  const void *header_bytes;
+  uint64_t header_bytes_len;
+  const uint64_t *header_pair_start; /* [nmsg+1] or NULL                                                   */
+  const tfgpu_header_pair *header_pairs;
+  int64_t npairs;
+} tfgpu_message_batch;
+
+/* raw_to_table_common.CommonConfig.  Types are "bytes" | "string" | "json"; key_type is looked at only when the key is enabled (Validate).  */
+typedef struct tfgpu_raw_to_table_config {
+  const char *table_name;          /* "" / NULL: the table is named after the topic                        */
+  int32_t is_key_enabled;
+  const char *key_type;
+  const char *value_type;
+  int32_t is_timestamp_enabled;
+  int32_t is_headers_enabled;
+  const char *dlq_suffix;          /* "" / NULL: "_dlq"; a suffix without a leading '_' is appended as it stands (base + "errors" = "baseerrors") */
+} tfgpu_raw_to_table_config;
+typedef struct tfgpu_raw_to_table tfgpu_raw_to_table;
+enum { TFGPU_RTT_MAIN = 0, TFGPU_RTT_DLQ = 1 };
+/* Host code, no GPU needed.  Validate's texts ("invalid parser config - unsupported key type: %s" / "… value type: %s") come back as
+ * TFGPU_ERR_CONFIG.  _create_json takes json.Marshal of ParserConfigRawToTableCommon or ParserConfigRawToTableLb (which has no key).           */
+int tfgpu_raw_to_table_create(const tfgpu_raw_to_table_config *cfg, tfgpu_raw_to_table **out);
+int tfgpu_raw_to_table_create_json(const char *config_json, tfgpu_raw_to_table **out);
+void tfgpu_raw_to_table_free(tfgpu_raw_to_table *h);
+/* BuildTableSchemaAndColumnNames(cfg, isDLQ): topic utf8, partition uint32, offset uint32 (keys, required), [timestamp (required)], [headers any],
+ * [key], value — DataType string for bytes, utf8 for string, any for JSON — and failure_reason utf8 in the dead-letter table.  Free with
+ * tfgpu_schema_free.                                                                                                                           */
+int tfgpu_raw_to_table_schema(const tfgpu_raw_to_table *h, int which, tfgpu_schema **out);
+/* ChangeItem.Table of the rows a batch of `topic` yields: TableName or the topic, plus the suffix for the dead-letter table.                   */
+int tfgpu_raw_to_table_table_name(const tfgpu_raw_to_table *h, int which, const char *topic, char *buf, size_t cap);
+/* RawToTableImpl.DoBatch: two ordinary batches, both in message order, all rows Insert, src_row[r] = the message index (the shim re-attaches LSN,
+ * CommitTime, Size and QueueMessageMeta from it).  *dlq_out has zero rows and its typed empty columns when nothing failed.
+ * Cells: offset = uint32(Message.Offset) (truncating); timestamp = time.Unix(0, write_time_ns); a nil Key / Value is a nil cell; string and
+ * bytes cells are the message's bytes; a JSON cell is an `any` — exactly the text tfgpu_sr_json_parse writes for an `any` property: json.Marshal of
+ * the value decoded with UseNumber (number tokens kept, strings re-encoded, a repeated key keeps its last value, keys ascending), and a top-level
+ * `null` is a nil cell.  headers is json.Marshal of the map[string]string: `{}` for a map without pairs, and the text `null` — a VALID cell —
+ * for a nil map: Go stores the nil map as a typed nil inside the interface, not as a nil interface.
+ * failure_reason is sendToDLQReason's text: key first, then value, joined with '|'.
+ * Messages the device does not decide — JSON nested deeper than 128 containers, or deeper than 16 with some object's keys not ascending — are in
+ * NEITHER batch: msg_codes[m] (HOST, [nmsg], may be NULL) = TFGPU_ROW_HOST_FALLBACK for them and TFGPU_ROW_OK for the rest, *nfallback their count.
+ * TFGPU_ERR_UNSUPPORTED, by name: values, keys, header bytes or an output text column reaching 4 GiB (32-bit offsets); more than 2^31-1 messages. */
+int tfgpu_raw_to_table_parse(const tfgpu_raw_to_table *h, const tfgpu_message_batch *batch, tfgpu_dbatch **main_out, tfgpu_dbatch **dlq_out,
+                             int32_t *msg_codes, int64_t *nfallback);
+/* the size refusals of tfgpu_raw_to_table_parse alone: judged from the lengths the batch states, before a byte is read (host code, no GPU)      */
+int tfgpu_raw_to_table_check_sizes(const tfgpu_message_batch *batch);
+/* the UTF-8 validator's geometry: bytes one lane takes of a long message per step, and the length from which the wave validates a message together */
+int tfgpu_rawtt_chunk_bytes(void);
+int tfgpu_rawtt_long_bytes(void);
+
 /* ---- profiling hooks (bench.py / rocprof cross-check) ------------------- */
 /* Per-kernel accumulated device time measured with HIP events on the library
  * stream.  Enable, run, then read back name/launches/total_ms.              */

@@ -142,6 +142,66 @@ class CMessages(C.Structure):
     _fields_ = [("nmsg", C.c_int64), ("start", C.c_void_p), ("offset", C.c_void_p), ("write_time_ns", C.c_void_p)]
 
 
+class CHeaderPair(C.Structure):
+    _fields_ = [("key_off", C.c_uint32), ("key_len", C.c_uint32), ("val_off", C.c_uint32), ("val_len", C.c_uint32)]
+
+
+class CMessageBatch(C.Structure):
+    _fields_ = [("topic", C.c_char_p), ("partition", C.c_uint32), ("mem", C.c_int32), ("nmsg", C.c_int64),
+                ("values", C.c_void_p), ("values_len", C.c_uint64), ("value_start", C.c_void_p),
+                ("keys", C.c_void_p), ("keys_len", C.c_uint64), ("key_start", C.c_void_p),
+                ("offset", C.c_void_p), ("write_time_ns", C.c_void_p),
+                ("value_nil", C.c_void_p), ("key_nil", C.c_void_p), ("headers_nil", C.c_void_p),
+                ("header_bytes", C.c_void_p), ("header_bytes_len", C.c_uint64), ("header_pair_start", C.c_void_p),
+                ("header_pairs", C.c_void_p), ("npairs", C.c_int64)]
+
+
+class CRawToTableConfig(C.Structure):
+    _fields_ = [("table_name", C.c_char_p), ("is_key_enabled", C.c_int32), ("key_type", C.c_char_p), ("value_type", C.c_char_p),
+                ("is_timestamp_enabled", C.c_int32), ("is_headers_enabled", C.c_int32), ("dlq_suffix", C.c_char_p)]
+
+
+RTT_MAIN, RTT_DLQ = 0, 1
+
+
+def message_batch(topic: str, partition: int, msgs) -> CMessageBatch:
+    """parsers.MessageBatch → tfgpu_message_batch in host memory.  msgs: [(offset, write_time_ns, key | None, value | None, headers | None)], headers a
+    dict (or a list of pairs, in the order given) of str / bytes → str / bytes.  None is Go's nil; b"" and {} are not."""
+    def raw(x):
+        return x.encode("utf-8") if isinstance(x, str) else bytes(x)
+    n = len(msgs)
+    vs, ks, ps = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+    off, wt = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.int64)
+    nil = np.zeros((3, n), bool)
+    vals, keys, hbytes, pairs = [], [], bytearray(), []
+    for i, (o, t, k, v, h) in enumerate(msgs):
+        off[i], wt[i] = o % (1 << 64), t
+        nil[0, i], nil[1, i], nil[2, i] = v is None, k is None, h is None
+        vals.append(v or b"")
+        keys.append(k or b"")
+        for hk, hv in (h.items() if isinstance(h, dict) else (h or [])):
+            hk, hv = raw(hk), raw(hv)
+            pairs.append((len(hbytes), len(hk), len(hbytes) + len(hk), len(hv)))
+            hbytes += hk + hv
+        vs[i + 1], ks[i + 1], ps[i + 1] = vs[i] + len(vals[-1]), ks[i] + len(keys[-1]), len(pairs)
+    vb = np.frombuffer(b"".join(vals) + b"\0", np.uint8).copy()
+    kb = np.frombuffer(b"".join(keys) + b"\0", np.uint8).copy()
+    hb = np.frombuffer(bytes(hbytes) + b"\0", np.uint8).copy()
+    pa = np.array(pairs if pairs else [(0, 0, 0, 0)], np.uint32)
+    bits = [np.packbits(nil[q], bitorder="little") if n else np.zeros(1, np.uint8) for q in range(3)]
+    b = CMessageBatch()
+    tp = topic.encode("utf-8")
+    b.topic, b.partition, b.mem, b.nmsg = tp, partition, MEM_HOST, n
+    b.values, b.values_len, b.value_start = vb.ctypes.data, int(vs[n]), vs.ctypes.data
+    b.keys, b.keys_len, b.key_start = kb.ctypes.data, int(ks[n]), ks.ctypes.data
+    b.offset, b.write_time_ns = off.ctypes.data, wt.ctypes.data
+    b.value_nil, b.key_nil, b.headers_nil = bits[0].ctypes.data, bits[1].ctypes.data, bits[2].ctypes.data
+    b.header_bytes, b.header_bytes_len, b.header_pair_start = hb.ctypes.data, len(hbytes), ps.ctypes.data
+    b.header_pairs, b.npairs = pa.ctypes.data, len(pairs)
+    b._keep = (tp, vs, ks, ps, off, wt, vb, kb, hb, pa, bits)
+    return b
+
+
 def json_options(add_rest=False, add_dedupe_keys=False, null_keys_allowed=False, use_numbers_in_any=False,
                  unescape_string_values=False, unpack_bytes_base64=False, ignore_column_paths=False, mark_dedupe_keys_as_system=False, topic="",
                  partition='{"partition":0,"topic":""}', format="json") -> CJsonOptions:

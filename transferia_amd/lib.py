@@ -36,6 +36,8 @@ EXPORTS = [
     "tfgpu_nginx_resolve_schema", "tfgpu_nginx_options_default", "tfgpu_nginx_parse", "tfgpu_nginx_tile_bytes", "tfgpu_nginx_workgroup_lines",
     "tfgpu_apply_meta", "tfgpu_table_split", "tfgpu_apply_split", "tfgpu_tablesplit_rows", "tfgpu_tablesplit_count", "tfgpu_tablesplit_name", "tfgpu_tablesplit_table_rows",
     "tfgpu_tablesplit_row_tables", "tfgpu_tablesplit_batch", "tfgpu_tablesplit_free",
+    "tfgpu_raw_to_table_create", "tfgpu_raw_to_table_create_json", "tfgpu_raw_to_table_free", "tfgpu_raw_to_table_schema", "tfgpu_raw_to_table_table_name",
+    "tfgpu_raw_to_table_parse", "tfgpu_raw_to_table_check_sizes", "tfgpu_rawtt_chunk_bytes", "tfgpu_rawtt_long_bytes",
 ]
 
 
@@ -168,6 +170,14 @@ def load():
     L.tfgpu_tablesplit_batch.argtypes = [P, C.c_int32, C.POINTER(P)]
     L.tfgpu_tablesplit_free.argtypes = [P]
     L.tfgpu_tablesplit_free.restype = None
+    L.tfgpu_raw_to_table_create.argtypes = [C.POINTER(abi.CRawToTableConfig), C.POINTER(P)]
+    L.tfgpu_raw_to_table_create_json.argtypes = [C.c_char_p, C.POINTER(P)]
+    L.tfgpu_raw_to_table_free.argtypes = [P]
+    L.tfgpu_raw_to_table_free.restype = None
+    L.tfgpu_raw_to_table_schema.argtypes = [P, C.c_int, C.POINTER(C.POINTER(abi.CSchema))]
+    L.tfgpu_raw_to_table_table_name.argtypes = [P, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]
+    L.tfgpu_raw_to_table_parse.argtypes = [P, C.POINTER(abi.CMessageBatch), C.POINTER(P), C.POINTER(P), P, C.POINTER(C.c_int64)]
+    L.tfgpu_raw_to_table_check_sizes.argtypes = [C.POINTER(abi.CMessageBatch)]
     _lib = L
     return L
 
@@ -1270,6 +1280,79 @@ def debezium_emit(opts: abi.CDbzEmitOptions, batch: DeviceBatch, meta: Optional[
                                       vs.ctypes.data, nul.ctypes.data, row.ctypes.data, cap, C.byref(n)))
     k = int(n.value)
     return DebeziumMessages(DeviceBuffer(ko), ks[:k + 1].copy(), DeviceBuffer(vo), vs[:k + 1].copy(), nul[:k].copy(), row[:k].copy())
+
+
+class RawToTable:
+    """The raw_to_table parser (pkg/parsers/registry/raw_to_table): create / schema / table_name are host code and need no GPU; parse runs the device."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def create(table_name: str = "", value_type: str = "bytes", key_type: Optional[str] = None, timestamp: bool = False, headers: bool = False,
+               dlq_suffix: str = "", is_key_enabled: Optional[bool] = None) -> "RawToTable":
+        """CommonConfig by its fields: the key is enabled when key_type is given (or is_key_enabled says so)"""
+        c = abi.CRawToTableConfig()
+        c.table_name, c.value_type, c.dlq_suffix = table_name.encode(), value_type.encode(), dlq_suffix.encode()
+        c.key_type = (key_type or "").encode()
+        c.is_key_enabled = int(key_type is not None if is_key_enabled is None else is_key_enabled)
+        c.is_timestamp_enabled, c.is_headers_enabled = int(timestamp), int(headers)
+        h = C.c_void_p()
+        _check(load().tfgpu_raw_to_table_create(C.byref(c), C.byref(h)))
+        return RawToTable(h)
+
+    @staticmethod
+    def from_config(config) -> "RawToTable":
+        """json.Marshal of ParserConfigRawToTableCommon / ParserConfigRawToTableLb (a dict or its text)"""
+        text = config if isinstance(config, (str, bytes)) else json.dumps(config)
+        h = C.c_void_p()
+        _check(load().tfgpu_raw_to_table_create_json(text.encode() if isinstance(text, str) else text, C.byref(h)))
+        return RawToTable(h)
+
+    def schema(self, which: int = abi.RTT_MAIN) -> abi.Schema:
+        out = C.POINTER(abi.CSchema)()
+        _check(load().tfgpu_raw_to_table_schema(self._h, which, C.byref(out)))
+        try:
+            return abi.Schema.from_c(out.contents)
+        finally:
+            load().tfgpu_schema_free(out)
+
+    def table_name(self, which: int, topic: str) -> str:
+        buf = C.create_string_buffer(len(topic.encode()) + 4096)
+        _check(load().tfgpu_raw_to_table_table_name(self._h, which, topic.encode(), buf, len(buf)))
+        return buf.value.decode()
+
+    def parse(self, batch: abi.CMessageBatch):
+        """RawToTableImpl.DoBatch → (main DeviceBatch, dead-letter DeviceBatch, [indexes of the messages left to the stock parser])"""
+        init()
+        codes = np.zeros(max(int(batch.nmsg), 1), np.int32)
+        m, d, nf = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        _check(load().tfgpu_raw_to_table_parse(self._h, C.byref(batch), C.byref(m), C.byref(d), codes.ctypes.data, C.byref(nf)))
+        fb = [int(i) for i in np.nonzero(codes[: int(batch.nmsg)] == abi.ROW_HOST_FALLBACK)[0]]
+        assert len(fb) == int(nf.value)
+        return DeviceBatch(m), DeviceBatch(d), fb
+
+    def free(self):
+        if self._h:
+            load().tfgpu_raw_to_table_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def raw_to_table_check_sizes(batch: abi.CMessageBatch):
+    """the size refusals of RawToTable.parse alone (host code)"""
+    _check(load().tfgpu_raw_to_table_check_sizes(C.byref(batch)))
+
+
+def rawtt_geometry():
+    """(chunk bytes, long bytes) of the UTF-8 validator"""
+    L = load()
+    return int(L.tfgpu_rawtt_chunk_bytes()), int(L.tfgpu_rawtt_long_bytes())
 
 
 def fqtn(ns: str, table: str) -> str:
