@@ -184,23 +184,11 @@ def test_tile_path_shapes(tf, oracle):
     compare(tf, oracle, dict(skip_rows=3, include_missing_columns=1), S4, normal, "skip3")
 
 
-def test_single_pass_form_and_its_fallbacks():
-    """The single-pass CSV form is opt-in (TFGPU_CSV_SPEC=1, read once per process): its own cases and the tile-shape stress run
-    in a process that has it on."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, TFGPU_CSV_SPEC="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k", "single_pass_cases or tile_path_shapes or hits_small or random_bytes"],
-                       env=env, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-3000:]
-
-
 def test_single_pass_cases(tf, oracle):
-    """A lane that has parsed a chunk of this shape sizes the next chunk's buffers from it — by default without waiting for
-    csv_count_newlines' total (the sized-ahead form), with TFGPU_CSV_SPEC=1 letting csv_parse_regular count the lines itself (no
-    csv_count_newlines pass); a chunk with more lines than expected, a header longer than the chunk's lines, or
-    a last line that spans the last tiles is parsed again the two-pass way.  Every answer must be the oracle's."""
+    """A lane that has parsed a chunk of this shape sizes the next chunk's buffers from it, without waiting for
+    csv_count_newlines' total (the sized-ahead form; TFGPU_CSV_AHEAD=0 turns it off); a chunk with more lines than expected,
+    a header longer than the chunk's lines, or a last line that spans the last tiles is parsed again with the count read back
+    first.  Every answer must be the oracle's."""
     rng = np.random.default_rng(SEED0 + 23)
     kw = dict(include_missing_columns=1)
 
@@ -217,23 +205,16 @@ def test_single_pass_cases(tf, oracle):
         tf.prof_reset()
         compare(tf, oracle, kw, S4, a, "same chunk again")
         k = kernels()
-        spec = _os.environ.get("TFGPU_CSV_SPEC") == "1"
-        ahead = not spec and _os.environ.get("TFGPU_CSV_AHEAD") != "0"   # the default: two passes, buffers sized ahead of the count
+        ahead = _os.environ.get("TFGPU_CSV_AHEAD") != "0"   # the default: two passes, buffers sized ahead of the count
 
         def launches(name):
             return sum(n for nm, n, _ms in tf.prof_get() if nm == name)
-        if spec:
-            assert "csv_parse_regular" in k and "csv_count_newlines" not in k, k
         tf.prof_reset()
         compare(tf, oracle, kw, S4, rows(5000, 9), "longer lines: fewer than expected")
-        if spec:
-            assert "csv_count_newlines" not in kernels()
         if ahead:
             assert launches("csv_count_newlines") == 1 and launches("csv_parse_regular") == 1
         tf.prof_reset()
         compare(tf, oracle, kw, S4, rows(20000, 1), "shorter lines: more than the buffers hold")
-        if spec:
-            assert "csv_count_newlines" in kernels()  # parsed again
         if ahead:
             assert launches("csv_count_newlines") == 2 and launches("csv_parse_regular") == 2   # parsed again, the count read back first
     finally:
@@ -265,20 +246,6 @@ def test_row_path_equals_tile_path():
     r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_csv.py", "-m", "gpu", "-q", "-x", "-k",
                         "edge_lines or typed_columns or random_bytes or tile_path_shapes or unmapped"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-
-
-def test_column_lane_form_equals_item_form():
-    """TFGPU_CSV_COL_LANES=2 (pieces of 8 columns): csv_parse_cols, the column-lane cell phase of the regular-tile kernel —
-    slower than the item form on the MI355X and off by default, kept with its measurements; it must pass the same cases."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, TFGPU_CSV_COL_LANES="2", TFGPU_CSV_COL_PIECE="8")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_csv.py", "-m", "gpu", "-q", "-x", "-k",
-                        "edge_lines or typed_columns or random_bytes or tile_path_shapes or unmapped or hits_small"],
-                       cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 
 

@@ -3,18 +3,23 @@
 // (strictify.go:18-181), producing typed Arrow-style columns in HBM without
 // ever materialising ChangeItems.
 //
-// Pipeline (all on the library stream):
-//   1. csv_count_newlines   : '\n' per 16 KiB tile                (reads B_csv)
-//   2. scan + csv_line_index: row_start[] of every complete line  (reads B_csv)
-//   3. csv_parse_rows       : one lane per row, wave-uniform loop over field
-//                             index; splitString state machine over an 8-byte
-//                             register window, typed parse of the fields the
-//                             schema maps, coalesced column-major stores;
-//                             string columns record (start,len)   (reads B_csv, writes B_fixed)
-//   4. segmented scan of string lengths → Arrow offsets
-//   5. csv_copy_strings     : unquote / ""-collapse copy           (reads ~B_str, writes B_str)
+// Pipeline (all on the library stream).  There is ONE tile path and one per-row path; csv_parse_body picks per chunk:
+//   1. csv_count_newlines      : '\n' per 1 KiB granule, then an exclusive scan: every tile's first line   (reads B_csv)
+//   2. csv_parse_regular       : a workgroup per 28 KiB tile of the plain shape (balanced quotes, every line the same
+//                                number of fields): byte classes, quote parity, field index in LDS, then the cells as
+//                                (column, line) items; text columns record (length, position)      (reads B_csv, writes B_fixed)
+//      csv_parse_tiles_general : the tiles it hands over whole (escapes, '\n' in quotes, ragged lines)
+//      csv_parse_listed        : the LINES either hands over (anything but a plain cell), one lane per line
+//      The buffers are sized from the count of step 1, or — sized-ahead form, the default for a lane that has seen a
+//      chunk of this shape — from the previous chunk's bytes per line before the count is known; a chunk that holds
+//      more lines sets CsvParams::ovf and is parsed again with the count read back first.
+//   2'. csv_line_index + csv_parse_rows: the per-row path, for options the tile kernels are not specialised for
+//      (TimestampParsers, DecimalPoint, NewlinesInValue, no quote character) and as the cross-check (TFGPU_CSV_ROWPATH=1)
+//   3. text stays a view into the source bytes (tf_textview.hpp) until a reader asks for it packed; the per-row path
+//      scans the lengths to Arrow offsets and copies at once (csv_copy_strings: unquote / ""-collapse)
 // Rows that fail (missing cell, cast, range, quote errors) are compacted out
 // and reported as tfgpu_row_error, mirroring how parseCSVRows drops them.
+// Variants of step 2 that were measured and rejected are not kept in the code: profiles/EXPERIMENTS.md §3.17–3.17c.
 //
 // HBM-bound byte kernel: algorithmic traffic B_csv + B_bin per row.
 #include <algorithm>
@@ -34,8 +39,9 @@
 #include "tf_plan.hpp"
 #include "tf_strictcell.hpp"
 
-// TFGPU_CSV_ABLATE=n (leave a kernel after phase n; results are NOT valid) is a profiling build only: the product's kernels carry none of
-// its branches (`if (CSV_ABL(t) == 31)` sat in every integer cell of the one kernel that is instruction-bound).
+// TFGPU_CSV_ABLATE=n (leave a kernel after phase n; results are NOT valid) and TFGPU_CSV_PHASES=1 (shader cycles per phase of
+// csv_parse_regular) are a profiling build only: the product's kernels carry none of their branches (`if (CSV_ABL(t) == 31)`
+// sat in every integer cell of the one kernel that is instruction-bound).
 // tools/build_variant.sh ablate tf_csv.hip -DTF_CSV_ABLATE_BUILD=1 builds the variant tools/ablate_csv.py and gpu_visit.sh ablate load.
 #ifdef TF_CSV_ABLATE_BUILD
 #define CSV_ABL(x) ((x).ablate)
@@ -284,7 +290,7 @@ struct CsvParams {
   int32_t nfields_used;        // max mapped field index + 1
   int32_t has_unmapped;        // some field index < nfields_used feeds no column
   const TCol *tcols;           // columns sorted by (kind, width): neighbouring lanes run one code path
-  unsigned long long *dbg_phase;  // TFGPU_CSV_PHASES=1 (profiling only): shader cycles per phase of csv_parse_regular, summed over its workgroups
+  unsigned long long *dbg_phase;  // TFGPU_CSV_PHASES=1 (profiling build only, like `ablate`): shader cycles per phase of csv_parse_regular, summed over its workgroups
   int32_t null_checks;         // strings_can_be_null || quoted_strings_can_be_null
   uint8_t *err;                // per row tfgpu_rowerr
   int32_t *err_col;
@@ -305,55 +311,11 @@ struct CsvParams {
   int32_t force_general;       // TFGPU_CSV_GENERAL=1: every tile takes the general kernel (parity cross-check of the two)
   const struct CsvRun *runs;   // tcols grouped into runs of one (kind, width)
   int32_t nruns;
-  // column-lane cell phase (csv_parse_regular): runs cut into tasks of at most 64 columns, each given to one wave
-  const struct CsvTask *tasks; // sorted by wave
-  const int32_t *wave_task;    // [9]: tasks of wave w are [wave_task[w], wave_task[w + 1])
-  int32_t col_lanes;           // 1: the cells run column-lane; 0: the item form (slots of 64 (column, line) items)
-  // csv_parse_lanes (lane = line): the column buffers as 4-byte offsets into one arena, dealt to the 16 waves in blocks
-  uint8_t *arena;
-  const uint32_t *lcols;       // [16 waves][64]: word 4 s + w of wave v = word w of its s-th column {p0 offset, p1 offset, field:16 | kind:8 | width:8, -}
-  const uint32_t *lwave_ncols; // [16]: columns per wave
-  uint32_t tile_cpt;           // 16-byte chunks per thread: the tile is 15, 30 or 45 KiB
-  // single-pass form (csv_parse_regular counts its own lines): [0] ticket counter, [1] overflow flag, [2 + t] state of tile t,
-  // [2 + ntiles + t] one past the last '\n' tile t owns (0: none)
-  uint32_t *spec;              // null: the line counts come from csv_count_newlines (gran_pre)
-  uint32_t cap_lines;          // lines the column buffers were sized for
   // sized-ahead form (two passes, no read-back between them): the host sized the buffers for cap_lines before csv_count_newlines
   // had finished; a tile whose lines end beyond that sets this word and writes nothing, and the host parses the chunk again
+  uint32_t cap_lines;          // lines the column buffers were sized for
   uint32_t *ovf;               // null: the buffers were sized from the true count
 };
-
-// ---- one pass instead of two: the tile kernel finds its first line's index itself ----------------------------------------
-// csv_count_newlines reads the whole chunk only to tell every tile how many lines precede it.  With `spec` set, tiles take
-// tickets in arrival order, each publishes the number of '\n' it owns as soon as it has classified its bytes, and one wave
-// looks back over its predecessors' words (Merrill & Garland's decoupled look-back: a word is empty, a tile's own count, or
-// the inclusive count up to and including the tile).  Tickets, not blockIdx: the tile with the lowest unfinished ticket is
-// always resident, so the wait cannot deadlock whatever order the dispatcher picks.  The host sizes the column buffers from
-// the previous chunk's bytes per line; a chunk with more lines than that sets the overflow word and is parsed again the
-// two-pass way.
-static constexpr uint32_t SP_AGG = 1u << 30, SP_INC = 2u << 30, SP_VAL = (1u << 30) - 1u;
-// all 64 lanes of ONE wave; returns the number of lines in front of tile `t` and leaves the tile's inclusive count published
-__device__ __forceinline__ uint32_t spec_lookback(uint32_t *state, int64_t t, uint32_t own, int lane) {
-  if (t == 0) { if (lane == 0) __atomic_store_n(&state[0], SP_INC | own, __ATOMIC_RELAXED); return 0u; }
-  if (lane == 0) __atomic_store_n(&state[t], SP_AGG | own, __ATOMIC_RELAXED);
-  uint32_t excl = 0;
-  int64_t base = t - 1;
-  for (;;) {
-    const int64_t idx = base - lane;
-    const uint32_t w = idx >= 0 ? __atomic_load_n(&state[idx], __ATOMIC_RELAXED) : SP_INC;
-    const uint64_t inc = __ballot((w >> 30) == 2u), empty = __ballot((w >> 30) == 0u);
-    const int fi = inc ? __ffsll((long long)inc) - 1 : 63;     // the nearest predecessor that already knows its inclusive count
-    const uint64_t need = fi == 63 ? ~0ull : ((2ull << fi) - 1ull);
-    if (empty & need) { __builtin_amdgcn_s_sleep(1); continue; }  // someone in between has not classified its bytes yet
-    uint32_t v = lane <= fi ? (w & SP_VAL) : 0u;
-    v = wave_scan_add(v);
-    excl += (uint32_t)__shfl((int)v, 63, 64);
-    if (inc) break;
-    base -= 64;
-  }
-  if (lane == 0) __atomic_store_n(&state[t], SP_INC | ((excl + own) & SP_VAL), __ATOMIC_RELAXED);
-  return excl;
-}
 
 // the typed half of a column descriptor, under the StrictKind `kind` (a CK_TIMESTAMP column is SK_TIME to Strictify)
 __device__ __forceinline__ StrictOut strict_out(const CsvCol &c, int32_t kind) { return StrictOut{kind, c.width, c.lo, c.hi, c.values, c.nanos}; }
@@ -700,7 +662,7 @@ __device__ __forceinline__ uint32_t qf_compose(uint32_t first, uint32_t then) {
 }
 
 // One piece: the lines whose '\n' lies in granules [gstart, gstart + gcount), gcount * CSV_GRAN <= CT_T.
-__device__ __forceinline__ void parse_tile_general(const CsvParams &p, const int64_t gstart, const int64_t gcount, const uint32_t spec_line0, const uint32_t spec_nlines) {
+__device__ __forceinline__ void parse_tile_general(const CsvParams &p, const int64_t gstart, const int64_t gcount) {
   __shared__ __attribute__((aligned(16))) uint8_t sb[CT_BYTES + 48];
   __shared__ uint16_t fpos[CT_FCAP];   // field-end position | bit15 = it is the line's '\n'
   __shared__ uint16_t rowend[CT_RCAP]; // ordinal of each line's last field
@@ -713,8 +675,8 @@ __device__ __forceinline__ void parse_tile_general(const CsvParams &p, const int
   __shared__ uint32_t wcnt[CT_THREADS / 64];
 
   const int64_t gend = min(gstart + gcount, p.ngran);
-  const uint32_t line0 = p.spec ? spec_line0 : p.gran_pre[gstart];
-  const uint32_t nlines = p.spec ? spec_nlines : p.gran_pre[gend] - line0;
+  const uint32_t line0 = p.gran_pre[gstart];
+  const uint32_t nlines = p.gran_pre[gend] - line0;
   if (nlines == 0) return;  // no line ends here (inside a very long line)
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1100,10 +1062,7 @@ __device__ __forceinline__ void parse_tile_general(const CsvParams &p, const int
     bstart = next_bstart;
     jb += nr; kb = kend + 1;
   }
-  if (tid == 0) {  // one past the last '\n' this tile owns
-    atomicMax(p.last_end, (uint32_t)(g0 + bstart));
-    if (p.spec) p.spec[2 + p.ntiles + gstart / (CT_T / CSV_GRAN)] = (uint32_t)(g0 + bstart);
-  }
+  if (tid == 0) atomicMax(p.last_end, (uint32_t)(g0 + bstart));  // one past the last '\n' this tile owns
 }
 
 // The tiles csv_parse_regular could not take (anything but the plain shape it is specialised for), one after another
@@ -1111,9 +1070,7 @@ __device__ __forceinline__ void parse_tile_general(const CsvParams &p, const int
 __global__ void __launch_bounds__(CT_THREADS, 6) csv_parse_tiles_general(CsvParams p) {
   const uint32_t n = *p.gen_n;
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const bool sp = p.spec != nullptr;
-    const uint32_t *e = p.gen_tile + (size_t)(sp ? 4 : 2) * i;
-    parse_tile_general(p, (int64_t)e[0], (int64_t)e[1], sp ? e[2] : 0u, sp ? e[3] : 0u);
+    parse_tile_general(p, (int64_t)p.gen_tile[2 * (size_t)i], (int64_t)p.gen_tile[2 * (size_t)i + 1]);
     __syncthreads();
   }
 }
@@ -1134,9 +1091,12 @@ __global__ void __launch_bounds__(CT_THREADS, 6) csv_parse_tiles_general(CsvPara
 // general code for the rest; (2) the byte classes chain their v_dot4 in pairs through the accumulator; (3) the escape
 // character is looked for where the tile's few quote characters are walked, not in every chunk; (4) the tile's line
 // counts arrive by scalar loads when the kernel starts — the two vector loads the epilogue used to issue waited for
-// every store of the cell phase (≈ 10 000 cycles of a workgroup's 46 000).  A lane-per-line / wave-per-column variant
-// with 44 KiB tiles was built and measured first (commit c60a587): a third fewer VALU instructions in the cells, but two
-// workgroups per CU instead of three, and 0.96 ms against this kernel's 0.75 before the changes above.
+// every store of the cell phase (≈ 10 000 cycles of a workgroup's 46 000).
+//
+// This is the one form of the kernel.  Four others were built, measured on the MI355X and found slower — a lane per line with a
+// wave per block of columns, column-lane cells inside this kernel, a single pass that counts its own lines through a decoupled
+// look-back, software-pipelined slots; their measurements, and the commit that last held their code, are in
+// profiles/EXPERIMENTS.md §3.17–3.17c.
 // ---------------------------------------------------------------------------
 // days since 1970-01-01 of a civil date with 0 <= y <= 9999, in 32-bit arithmetic (constant divisors only)
 __device__ __forceinline__ int32_t days_from_civil32(uint32_t y, uint32_t m, uint32_t d) {
@@ -1158,12 +1118,11 @@ static constexpr int CR_FCAP = TF_CR_FCAP;   // field ends the regular kernel in
 static constexpr int CR_LCOLS = 128;   // columns whose descriptors it stages in LDS
 static constexpr uint32_t CR_KDUMMY = CR_FCAP + 2;  // index slot of the empty field idle lanes read
 struct CsvRun { int32_t kind, width, first, ncols; };  // consecutive tcols of one (kind, width); kind -1: DefaultValue columns (no field)
-struct CsvTask { int32_t kind, width, first, ncols; };  // a piece of a run of the fast kinds (integers, text, date / timestamp): ncols <= 64
 
 // what the cell loops of csv_parse_regular share
 struct RegTile {
   const uint8_t *sb; const uint16_t *fposx; const uint32_t *qmask; const uint16_t *qpre; const uint2 *keeptab; uint8_t *slowf; const uint64_t *colp0, *colp1; const uint16_t *colfield;
-  uint32_t nr, NF, step_q, step_r; float inv_nr; int32_t row0; uint32_t g0; uint32_t quote; bool double_quote; int32_t ablate; int32_t col_mode;
+  uint32_t nr, NF, step_q, step_r; float inv_nr; int32_t row0; uint32_t g0; uint32_t quote; bool double_quote; int32_t ablate;
 };
 // one cell of a run: item → (column, line), its output row and its byte range [fs, fend) in the tile
 struct RegCell { bool on; uint32_t col, jj, fs, fend; int32_t r; };
@@ -1196,29 +1155,14 @@ __device__ __forceinline__ RegCell reg_cell(const RegTile &t, uint32_t first_col
   c.fs = (uint32_t)t.fposx[kr] + 1; c.fend = t.fposx[kr1];
   return c;
 }
-// A wave's slots of one run.  TF_CSV_PREFETCH=1 (A/B builds) reads the NEXT slot's index entries before the current slot's body runs,
-// so that the two ds_read_u16 of slot s + 8 ride under slot s's arithmetic instead of heading its dependent chain (index → window →
-// store).  Measured (gpurun r08g): 1.04-1.09 ms against 0.74 — the kernel sits at the 80 VGPRs six waves per SIMD allow, the second
-// cell in flight spills 76 bytes per lane to scratch.  Off.
-#ifndef TF_CSV_PREFETCH
-#define TF_CSV_PREFETCH 0
-#endif
+// A wave's slots of one run.  (Reading the next slot's index entries under the current slot's body was measured and is slower:
+// the kernel sits at the 80 VGPRs six waves per SIMD allow — profiles/EXPERIMENTS.md.)
 template <class Body> __device__ __forceinline__ void for_slots(const RegTile &t, const CsvRun &run, uint32_t sbase, int wv, int lane, Body body) {
   const uint32_t items = (uint32_t)run.ncols * t.nr, nslots = (items + 63) >> 6, end = sbase + nslots;
   const uint32_t s0 = sbase + (((uint32_t)wv - sbase) & (CT_WAVES - 1u));
   if (s0 >= end) return;
   ItemIter x = item_first(t, (s0 - sbase) * 64 + (uint32_t)lane);
-#if TF_CSV_PREFETCH
-  RegCell c = reg_cell(t, (uint32_t)run.first, x, items);
-  for (uint32_t s = s0; s < end; s += CT_WAVES) {
-    RegCell cn = c;
-    if (s + CT_WAVES < end) { item_next(t, x); cn = reg_cell(t, (uint32_t)run.first, x, items); }  // (wave-uniform)
-    body(c);
-    c = cn;
-  }
-#else
   for (uint32_t s = s0; s < end; s += CT_WAVES, item_next(t, x)) body(reg_cell(t, (uint32_t)run.first, x, items));
-#endif
 }
 // the column buffers are device allocations: say so, or the pointer read back from LDS makes every store a flat_store
 template <class T> __device__ __forceinline__ T *global_ptr(uint64_t p) { return TF_GLOBAL_PTR(T, p); }
@@ -1414,59 +1358,7 @@ template <int KIND> __device__ __forceinline__ void reg_cells_time(const RegTile
   });
 }
 
-// ---- the column-lane form of the cell phase -----------------------------------------------------------------------------------
-// A wave takes a TASK: G <= 64 columns of one (kind, width).  Lane l owns column first + l % G for the whole task and the lines
-// jj = it * P + l / G (P = 64 / G lines per step), so everything a cell's column fixes — its field ordinal, its output pointers —
-// is read ONCE per task into the lane's registers, and a step's skeleton is: the line (one add), the index entry (one mad), two
-// index reads, the row.  The item form pays per cell for the (column, line) of a slot item (a carry chain), three descriptor reads
-// from LDS and the slot bookkeeping of every run in every wave.  A lane's stores go to its own column: a wave store touches G
-// cache lines with P consecutive values each (the tile's 35 lines of a column are 70-280 contiguous bytes: they meet in L2).
-struct LaneCol { uint32_t g, ph, P; bool live; };  // P is wave-uniform (a scalar): the step loops below are scalar loops
-__device__ __forceinline__ LaneCol lane_col(const CsvTask &k, int lane, int mode) {
-  const uint32_t G = (uint32_t)__builtin_amdgcn_readfirstlane(k.ncols), P = 64u / G;
-  if (mode == 2) {  // a column's P lines on NEIGHBOURING lanes: a wave store is G runs of P consecutive values
-    const uint32_t g = (uint32_t)((uint32_t)lane * (65536u / P + 1u)) >> 16;  // lane / P
-    return LaneCol{g, (uint32_t)lane - g * P, P, g < G};
-  }
-  const uint32_t ph = (uint32_t)((uint32_t)lane * (65536u / G + 1u)) >> 16;  // lane / G for lane < 64 (G <= 64)
-  return LaneCol{(uint32_t)lane - ph * G, ph, P, ph < P};
-}
-__device__ __forceinline__ RegCell lane_cell(const RegTile &t, const LaneCol &lc, uint32_t jj0, uint32_t colfield) {
-  RegCell c;
-  c.jj = jj0 + lc.ph; c.col = 0;
-  c.r = t.row0 + (int32_t)c.jj;
-  c.on = lc.live && c.jj < t.nr && c.r >= 0;  // header lines produce nothing
-  const uint32_t kr = c.on ? __umul24(c.jj, t.NF) + colfield : CR_KDUMMY;
-  uint32_t kr1 = kr + 1;
-  TF_OPAQUE(kr1);  // (two ds_read_u16: see reg_cell)
-  c.fs = (uint32_t)t.fposx[kr] + 1; c.fend = t.fposx[kr1];
-  return c;
-}
-template <int KIND, int W> __device__ __forceinline__ void task_cells_int(const RegTile &t, const CsvTask &k, int lane) {
-  using T = std::conditional_t<W == 1, int8_t, std::conditional_t<W == 2, int16_t, std::conditional_t<W == 4, int32_t, int64_t>>>;
-  const LaneCol lc = lane_col(k, lane, t.col_mode);
-  const uint32_t col = (uint32_t)k.first + (lc.live ? lc.g : 0u);
-  const uint32_t colfield = t.colfield[col];
-  T *const out = global_ptr<T>(t.colp0[col]);
-  for (uint32_t jj0 = 0; jj0 < t.nr; jj0 += lc.P) reg_int_body<KIND, W, T>(t, lane_cell(t, lc, jj0, colfield), out);
-}
-__device__ __forceinline__ void task_cells_str(const RegTile &t, const CsvTask &k, int lane) {
-  const LaneCol lc = lane_col(k, lane, t.col_mode);
-  const uint32_t col = (uint32_t)k.first + (lc.live ? lc.g : 0u);
-  const uint32_t colfield = t.colfield[col];
-  uint32_t *const lens = global_ptr<uint32_t>(t.colp0[col]), *const fstart = global_ptr<uint32_t>(t.colp1[col]);
-  for (uint32_t jj0 = 0; jj0 < t.nr; jj0 += lc.P) reg_str_body(t, lane_cell(t, lc, jj0, colfield), lens, fstart);
-}
-template <int KIND> __device__ __forceinline__ void task_cells_time(const RegTile &t, const CsvTask &k, int lane) {
-  const LaneCol lc = lane_col(k, lane, t.col_mode);
-  const uint32_t col = (uint32_t)k.first + (lc.live ? lc.g : 0u);
-  const uint32_t colfield = t.colfield[col];
-  int64_t *const sec = global_ptr<int64_t>(t.colp0[col]); int32_t *const nanos = global_ptr<int32_t>(t.colp1[col]);
-  for (uint32_t jj0 = 0; jj0 < t.nr; jj0 += lc.P) reg_time_body<KIND>(t, lane_cell(t, lc, jj0, colfield), sec, nanos);
-}
-__device__ __forceinline__ bool task_kind(int kind) { return kind == CK_INT || kind == CK_UINT || kind == CK_STR || kind == CK_DATE || kind == CK_TIMESTAMP; }
-
-template <bool COLS> __device__ __forceinline__ void csv_parse_regular_body(const CsvParams &p) {
+__device__ __forceinline__ void csv_parse_regular_body(const CsvParams &p) {
   static_assert(CT_SPILL == 64 * CT_CPT * 16, "the look-behind window is exactly wave 0's bytes");
   __shared__ __attribute__((aligned(16))) uint8_t sbuf[32 + CT_BYTES + 48];  // 32 bytes in front: the 24-byte window of a cell that ends within the tile's first bytes
   __shared__ uint16_t fposx[CR_FCAP + 4];    // [k + 1] = end of field k; [0] = first line's start - 1; [CR_KDUMMY], [CR_KDUMMY + 1]: an empty field for idle lanes
@@ -1481,48 +1373,36 @@ template <bool COLS> __device__ __forceinline__ void csv_parse_regular_body(cons
   __shared__ uint32_t wpar[CT_THREADS / 64];
   __shared__ uint32_t wcnt[CT_THREADS / 64];
   __shared__ uint32_t misc[4];               // 0: first line's start, 1: tile is not regular, 2: NF
-  __shared__ uint32_t spec_sh[2];            // single-pass form: 0 = this workgroup's ticket, 1 = lines in front of its tile
   uint8_t *const sb = sbuf + 32;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const bool spec = p.spec != nullptr;
 
-  int64_t tile;
-  if (spec) {  // tiles in arrival order (see spec_lookback)
-    if (tid == 0) spec_sh[0] = atomicAdd(p.spec, 1u);
-    __syncthreads();
-    tile = (int64_t)spec_sh[0];
-  } else {  // XCD-aware tile order: consecutive tiles (which share their look-behind bytes) run on one XCD's L2
-    const int64_t per_xcd = (p.ntiles + 7) / 8;
-    tile = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  }
+  // XCD-aware tile order: consecutive tiles (which share their look-behind bytes) run on one XCD's L2
+  const int64_t per_xcd = (p.ntiles + 7) / 8;
+  const int64_t tile = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
   if (tile >= p.ntiles) return;
   // the tile's lines from the exclusive scan of the newline counts per 4 KiB granule: wave-uniform addresses, read by the
   // scalar unit now — a vector load at the end of the kernel would wait for every store of the cell phase
   constexpr int64_t GPT = CT_T / CSV_GRAN;
   const int64_t gr0 = tile * GPT, gr1 = min(gr0 + GPT, p.ngran);
   const auto *gpre = TF_CONST_PTR(uint32_t, p.gran_pre);
-  uint32_t line0 = 0, line1 = 0, lines_all = 0, nlines = 0;
-  if (!spec) {
-    line0 = gpre[gr0]; line1 = gpre[gr1]; lines_all = gpre[p.ngran];
-    nlines = line1 - line0;
-    if (nlines == 0) return;  // no line ends here (inside a very long line)
-    if (p.ovf && line1 > p.cap_lines) { if (tid == 0) *p.ovf = 1u; return; }  // sized-ahead form: more lines than the buffers hold (uniform)
-  }
+  const uint32_t line0 = gpre[gr0], line1 = gpre[gr1], lines_all = gpre[p.ngran], nlines = line1 - line0;
+  if (nlines == 0) return;  // no line ends here (inside a very long line)
+  if (p.ovf && line1 > p.cap_lines) { if (tid == 0) *p.ovf = 1u; return; }  // sized-ahead form: more lines than the buffers hold (uniform)
   const CsvOpts &o = p.o;
   const int64_t g0 = tile * CT_T - CT_SPILL;  // absolute offset of sb[0]
-  // a piece for the general kernel: (first granule, granules) and, in the single-pass form, (first line, lines)
+  // a piece for the general kernel: (first granule, granules)
   auto give_up = [&]() {
-    if (tid == 0) {
-      const uint32_t slot = atomicAdd(p.gen_n, 1u);
-      if (spec) { p.gen_tile[4 * slot] = (uint32_t)gr0; p.gen_tile[4 * slot + 1] = (uint32_t)(gr1 - gr0); p.gen_tile[4 * slot + 2] = line0; p.gen_tile[4 * slot + 3] = nlines; }
-      else { p.gen_tile[2 * slot] = (uint32_t)gr0; p.gen_tile[2 * slot + 1] = (uint32_t)(gr1 - gr0); }
-    }
+    if (tid == 0) { const uint32_t slot = atomicAdd(p.gen_n, 1u); p.gen_tile[2 * slot] = (uint32_t)gr0; p.gen_tile[2 * slot + 1] = (uint32_t)(gr1 - gr0); }
   };
+#ifdef TF_CSV_ABLATE_BUILD
   unsigned long long tstamp = p.dbg_phase ? (unsigned long long)__builtin_amdgcn_s_memtime() : 0ull;
-  auto phase = [&](int k) {  // TFGPU_CSV_PHASES=1, profiling only: thread 0 adds the cycles since the previous stamp to slot k
+  auto phase = [&](int k) {  // TFGPU_CSV_PHASES=1, profiling build only: thread 0 adds the cycles since the previous stamp to slot k
     if (p.dbg_phase && tid == 0) { const unsigned long long now = (unsigned long long)__builtin_amdgcn_s_memtime(); atomicAdd(p.dbg_phase + k, now - tstamp); tstamp = now; }
   };
-  if (!spec && (p.force_general || nlines > (uint32_t)CT_RCAP || p.ncols > CR_LCOLS)) { give_up(); return; }  // (the host does not pick the single-pass form with force_general or that many columns)
+#else
+  auto phase = [](int) {};
+#endif
+  if (p.force_general || nlines > (uint32_t)CT_RCAP || p.ncols > CR_LCOLS) { give_up(); return; }
 
   // ---- stage: coalesced 16 B/lane ----
   if (g0 >= 0 && (uint64_t)(g0 + CT_BYTES) <= p.len) {
@@ -1628,21 +1508,7 @@ template <bool COLS> __device__ __forceinline__ void csv_parse_regular_body(cons
   uint32_t cpre = 0, ctot = 0;
   for (int i = 0; i < CT_THREADS / 64; i++) { const uint32_t x = wcnt[i]; if (i < wv) cpre += x; ctot += x; }
   const uint32_t nfe = ctot & 0xFFFFu, nr = ctot >> 16;
-  if (spec) {
-    // the tile's own count is final here, whatever becomes of the tile: publish it and find the lines in front.  The last wave
-    // does it (its value reaches the others at the next barrier); on the early exits below it is the one that stays.
-    nlines = nr;
-    const bool quit = misc[1] || nfe > (uint32_t)CR_FCAP || nr > (uint32_t)CT_RCAP || nr == 0;
-    if (wv == CT_THREADS / 64 - 1) {
-      line0 = spec_lookback(p.spec + 2, tile, nr, lane);
-      if (lane == 0) spec_sh[1] = line0;
-      if (quit && nr != 0 && lane == 0) {
-        if (line0 + nr > p.cap_lines) p.spec[1] = 1u;
-        else { const uint32_t slot = atomicAdd(p.gen_n, 1u); p.gen_tile[4 * slot] = (uint32_t)gr0; p.gen_tile[4 * slot + 1] = (uint32_t)(gr1 - gr0); p.gen_tile[4 * slot + 2] = line0; p.gen_tile[4 * slot + 3] = nr; }
-      }
-    }
-    if (quit) return;
-  } else if (misc[1] || nfe > (uint32_t)CR_FCAP || nr != nlines) { give_up(); return; }  // uniform: LDS flags were written before the barrier
+  if (misc[1] || nfe > (uint32_t)CR_FCAP || nr != nlines) { give_up(); return; }  // uniform: LDS flags were written before the barrier
   const uint32_t frs = misc[0];
   if (CSV_ABL(p) == 3) { if (fe[0] + fe[1] + fe[2] + fe[3] == 0xFFFFFFFFu) p.err[0] = 1; return; }
 
@@ -1687,10 +1553,6 @@ template <bool COLS> __device__ __forceinline__ void csv_parse_regular_body(cons
   __syncthreads();
   phase(3);
   if (CSV_ABL(p) == 4) return;
-  if (spec) {
-    line0 = spec_sh[1]; line1 = line0 + nr;
-    if (line1 > p.cap_lines) { if (tid == 0) p.spec[1] = 1u; return; }  // more lines than the buffers were sized for: the host parses the chunk again
-  }
   const uint32_t NF = misc[2];  // fields of the first line; every line must have as many
   if (NF < 2 || NF < (uint32_t)p.nfields_used || nr * NF > nfe) { give_up(); return; }  // uniform.  (A lone "\n" is a line of no fields, reader.go:146-150.)
   for (uint32_t jj = tid; jj < nr; jj += CT_THREADS) {
@@ -1705,33 +1567,10 @@ template <bool COLS> __device__ __forceinline__ void csv_parse_regular_body(cons
     RegTile t;
     t.sb = sb; t.fposx = fposx; t.qmask = qmask; t.qpre = qpre; t.keeptab = keeptab; t.slowf = slowf; t.colp0 = colp0; t.colp1 = colp1; t.colfield = colfield;
     t.nr = nr; t.NF = NF; t.step_q = 64u * CT_WAVES / nr; t.step_r = 64u * CT_WAVES - t.step_q * nr; t.inv_nr = __uint_as_float(__float_as_uint(1.0f / (float)nr) - 2u);  // a hair below 1 / nr: the quotient estimate never overshoots
-    t.row0 = (int32_t)((int64_t)line0 - p.skip_rows); t.g0 = (uint32_t)g0; t.quote = o.quote; t.double_quote = o.double_quote != 0; t.ablate = CSV_ABL(p); t.col_mode = p.col_lanes;
-    if constexpr (COLS) {
-      for (int ti = p.wave_task[wv]; ti < p.wave_task[wv + 1]; ti++) {
-        const CsvTask k = p.tasks[ti];
-        if (CSV_ABL(p) >= 10) {  // 10: no cells; 11: integer tasks only; 12: text; 13: date / timestamp
-          const int grp = (k.kind == CK_INT || k.kind == CK_UINT) ? 11 : k.kind == CK_STR ? 12 : 13;
-          if (CSV_ABL(p) != grp && !(CSV_ABL(p) == 31 && grp == 11)) continue;
-        }
-        switch (k.kind) {
-          case CK_INT:
-            if (k.width == 1) task_cells_int<CK_INT, 1>(t, k, lane); else if (k.width == 2) task_cells_int<CK_INT, 2>(t, k, lane);
-            else if (k.width == 4) task_cells_int<CK_INT, 4>(t, k, lane); else task_cells_int<CK_INT, 8>(t, k, lane);
-            break;
-          case CK_UINT:
-            if (k.width == 1) task_cells_int<CK_UINT, 1>(t, k, lane); else if (k.width == 2) task_cells_int<CK_UINT, 2>(t, k, lane);
-            else if (k.width == 4) task_cells_int<CK_UINT, 4>(t, k, lane); else task_cells_int<CK_UINT, 8>(t, k, lane);
-            break;
-          case CK_STR: task_cells_str(t, k, lane); break;
-          case CK_DATE: task_cells_time<CK_DATE>(t, k, lane); break;
-          default: task_cells_time<CK_TIMESTAMP>(t, k, lane);
-        }
-      }
-    }
+    t.row0 = (int32_t)((int64_t)line0 - p.skip_rows); t.g0 = (uint32_t)g0; t.quote = o.quote; t.double_quote = o.double_quote != 0; t.ablate = CSV_ABL(p);
     uint32_t sbase = 0;
     for (int ri = 0; ri < p.nruns; ri++) {
       const CsvRun run = p.runs[ri];
-      if (COLS && task_kind(run.kind)) continue;  // its cells ran as tasks
       const uint32_t items = (uint32_t)run.ncols * nr, nslots = (items + 63) >> 6;
       if (CSV_ABL(p) >= 10) {  // 10: no cells; 11: integer runs only; 12: text runs only; 13: date / timestamp runs only
         const int grp = (run.kind == CK_INT || run.kind == CK_UINT) ? 11 : run.kind == CK_STR ? 12 : 13;
@@ -1795,17 +1634,12 @@ template <bool COLS> __device__ __forceinline__ void csv_parse_regular_body(cons
     } else p.err[r] = 0;
   }
   // one past the last '\n' of the chunk: only the tile that owns the last line has it (30 000 atomics on one word are not free)
-  // (single-pass form: nobody knows the total yet; every tile leaves its own last '\n', csv_collect takes the last tile's that has one)
-  if (tid == 0) { if (spec) p.spec[2 + p.ntiles + tile] = (uint32_t)(g0 + fposx[nr * NF] + 1); else if (line1 == lines_all) atomicMax(p.last_end, (uint32_t)(g0 + fposx[nr * NF] + 1)); }
+  if (tid == 0 && line1 == lines_all) atomicMax(p.last_end, (uint32_t)(g0 + fposx[nr * NF] + 1));
   phase(6);
 }
 
-// the kernel of the bench line: the item form of the cell phase
-__global__ void __launch_bounds__(CT_THREADS, 6) csv_parse_regular(CsvParams p) { csv_parse_regular_body<false>(p); }
-// … and with the column-lane form (TFGPU_CSV_COL_LANES=1 | 2): built, measured, slower — see the host code
-__global__ void __launch_bounds__(CT_THREADS, 6) csv_parse_cols(CsvParams p) { csv_parse_regular_body<true>(p); }
-
-#include "tf_csv_lanes.inc"
+// the kernel of the bench line
+__global__ void __launch_bounds__(CT_THREADS, 6) csv_parse_regular(CsvParams p) { csv_parse_regular_body(p); }
 
 // rows that failed contribute no string bytes
 // (sized-ahead form: `nrows` is what the buffers were sized for, err[] beyond the true count — lines_total - skip — was written by nobody)
@@ -1912,29 +1746,15 @@ __global__ void __launch_bounds__(256) csv_copy_special(CopyParams p) {
 }
 
 // one contiguous summary for a single read-back: [nerr, consumed, total bytes of each string column]
-// (single-pass form: `nrows` is what the buffers were sized for; the true count is the last tile's inclusive line count)
 __global__ void csv_collect(const uint32_t *nerr, const uint32_t *last, const uint32_t *lens_all, int64_t seg_stride, int64_t nrows, int nstr, const uint32_t *fstart_all,
-                            int64_t fstride, uint32_t *out, const uint32_t *spec, int64_t ntiles, int64_t skip, const uint32_t *lines_total, const uint32_t *ovf) {
+                            int64_t fstride, uint32_t *out, int64_t skip, const uint32_t *lines_total, const uint32_t *ovf) {
   int i = threadIdx.x;
   if (ovf) {  // sized-ahead form: `nrows` is what the buffers were sized for; the true count is csv_count_newlines' total
     const uint32_t nl = *lines_total;
     if (i == 2) { out[2 + 2 * nstr] = nl; out[3 + 2 * nstr] = *ovf; }
     nrows = min(nrows, max((int64_t)nl - skip, (int64_t)0));
-    if (i == 1) out[1] = *last;
-  } else if (spec) {
-    const uint32_t nl = ntiles ? (spec[2 + ntiles - 1] & SP_VAL) : 0u;
-    if (i == 2) { out[2 + 2 * nstr] = nl; out[3 + 2 * nstr] = spec[1]; }
-    nrows = min(nrows, max((int64_t)nl - skip, (int64_t)0));
-    // the chunk's last '\n': the highest tile that owns one (all 64 lanes)
-    uint32_t le = 0;
-    for (int64_t hi = ntiles - 1; hi >= 0 && le == 0; hi -= 64) {
-      const int64_t t = hi - i;
-      const uint32_t v = t >= 0 ? spec[2 + ntiles + t] : 0u;
-      const uint64_t has = __ballot(v != 0);
-      if (has) le = (uint32_t)__shfl((int)v, __ffsll((long long)has) - 1, 64);
-    }
-    if (i == 1) out[1] = le;
-  } else if (i == 1) out[1] = *last;
+  }
+  if (i == 1) out[1] = *last;
   if (i == 0) out[0] = *nerr;
   for (int s = i; s < nstr; s += blockDim.x) { out[2 + s] = lens_all ? lens_all[(int64_t)s * seg_stride + nrows] : 0u; out[2 + nstr + s] = fstart_all[(int64_t)s * fstride + FS_HDR - 1]; }  // (lens_all null: the lengths stay unscanned, there are no totals)
 }
@@ -2207,10 +2027,10 @@ extern "C" void tfgpu_csv_options_default(tfgpu_csv_options *o) {  // csv.NewRea
 }
 
 
-// `allow_spec`: the single-pass form may be used (csv_parse_regular counts its own lines, the buffers sized from the lane's
-// previous chunk).  *retry = the chunk held more lines than that (or ended oddly): nothing was returned, call again without it.
+// `allow_ahead`: the sized-ahead form may be used (the buffers sized from the lane's previous chunk, before the line count is known).
+// *retry = the chunk held more lines than that (or ended oddly): nothing was returned, call again without it.
 static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *schema, const void *bytes, uint64_t len, int mem,
-                          tfgpu_dbatch **out, uint64_t *consumed, tfgpu_row_error *errs, int64_t errs_cap, int64_t *nerrs, bool allow_spec, bool *retry) {
+                          tfgpu_dbatch **out, uint64_t *consumed, tfgpu_row_error *errs, int64_t errs_cap, int64_t *nerrs, bool allow_ahead, bool *retry) {
   TF_API_BEGIN
   if (!opts || !schema || !out) return tf::fail(TFGPU_ERR_INVALID, "tfgpu_csv_parse: null argument");
   if (len >= 0x7FFFFFF0ull) return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_csv_parse: chunk must be < 2 GiB (the reference reads 20 MiB chunks, chunk_reader.go:12)");
@@ -2272,32 +2092,23 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   // the tile kernels are specialised for the plain shape of the options; the rest takes the per-row path, which carries every rule
   const bool rowpath = force_rowpath || opts->escape_char == '\n' || opts->escape_char >= 0x80 || opts->quote_char >= 0x80 || opts->quote_char == 0 ||
                        opts->n_timestamp_parsers > 0 || !dp.empty() || multiline;
-  // ---- the single-pass form (TFGPU_CSV_SPEC=1): a lane that has parsed a chunk of this shape before sizes the buffers from that
-  //      chunk's bytes per line (+ 1/16) and lets the tile kernel count; more lines than that → *retry.
-  //      OFF by default.  Measured on the MI355X (profiles/r06s_ab_csv_*.json): the count pass and its read-back go (0.163 + 0.014 ms)
-  //      but csv_parse_regular grows from 0.728 to 1.014 ms — a ticket and a look-back are three to five dependent round trips
-  //      to memory-side coherent words (the eight XCDs share no L2), ~8 us per workgroup of a 20 us lifetime, and with three
-  //      workgroups per CU there is nobody to hide them behind.  The step: 1.77 ms two-pass, 1.89 ms single-pass. ----
-  static const bool spec_off = [] { const char *e = std::getenv("TFGPU_CSV_SPEC"); return !(e && e[0] == '1'); }();
-  static const bool spec_blockers = [] { for (const char *n : {"TFGPU_CSV_ABLATE", "TFGPU_CSV_GENERAL", "TFGPU_CSV_PHASES", "TFGPU_CSV_LANES"}) { const char *e = std::getenv(n); if (e && e[0] && e[0] != '0') return true; } return false; }();
-  const bool spec = allow_spec && !spec_off && !spec_blockers && !rowpath && schema->ncols <= CR_LCOLS && cx.csv_hint_ncols == schema->ncols && cx.csv_hint_bpl >= 1.0 &&
-                    len >= 2 * (uint64_t)CT_T && len < (1ull << 30);
   // ---- the sized-ahead form (default; TFGPU_CSV_AHEAD=0 turns it off): the two passes as they are, but a lane that has parsed a chunk
   //      of this shape before sizes the buffers from that chunk's bytes per line (+ 1/16) and does NOT wait for the count — the column plan
   //      below is made while csv_count_newlines runs, the tile kernel is queued behind it, and the true count arrives with the one
   //      read-back at the end.  A tile whose lines end beyond the buffers sets a flag and writes nothing → *retry. ----
   static const bool ahead_off = [] { const char *e = std::getenv("TFGPU_CSV_AHEAD"); return e && e[0] == '0'; }();
-  const bool ahead = allow_spec && !ahead_off && !spec && !spec_blockers && !rowpath && cx.csv_hint_ncols == schema->ncols && cx.csv_hint_bpl >= 1.0 &&
+  static const bool ahead_blockers = [] { for (const char *n : {"TFGPU_CSV_ABLATE", "TFGPU_CSV_GENERAL", "TFGPU_CSV_PHASES"}) { const char *e = std::getenv(n); if (e && e[0] && e[0] != '0') return true; } return false; }();
+  const bool ahead = allow_ahead && !ahead_off && !ahead_blockers && !rowpath && cx.csv_hint_ncols == schema->ncols && cx.csv_hint_bpl >= 1.0 &&
                      len >= 2 * (uint64_t)CT_T && len < (1ull << 30);
   uint32_t cap_lines = 0;
-  Buf tile_counts = dalloc((size_t)((spec ? 0 : ngran) + 1) * 4);
+  Buf tile_counts = dalloc((size_t)(ngran + 1) * 4);
   uint32_t nlines = 0;
-  if (spec || ahead) {
+  if (ahead) {
     const double est = (double)len / cx.csv_hint_bpl;
     cap_lines = (uint32_t)std::min<double>((double)len, est + est / 16.0 + 64.0);
     nlines = cap_lines;  // everything below is sized for this many; the true count arrives with the summary
   }
-  if (!spec && ntiles) {
+  if (ntiles) {
     { KernelTimer t("csv_count_newlines"); csv_count_newlines<<<(unsigned)ntiles, NL_THREADS, 0, st>>>(data, len, ptr<uint32_t>(tile_counts), ngran); }
     exclusive_scan_u32(ptr<uint32_t>(tile_counts), ptr<uint32_t>(tile_counts), ngran, true);
     if (!ahead) {
@@ -2441,11 +2252,9 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   // lines the tile path hands to the per-row path (at most one per tile per pass) + consumed offset
   const int64_t slow_cap = (int64_t)nlines + 5 * (ngran + 1) + 8;  // every line at most once, plus long / over-wide ones per piece
   Buf slow = dalloc((size_t)(2 * slow_cap + 2) * 4);
-  Buf gen = dalloc((size_t)(4 * (ngran + 2) + 2) * 4);  // [0] = count, then (first granule, granules) pairs — with (first line, lines) in the single-pass form
+  Buf gen = dalloc((size_t)(2 * (ngran + 2) + 2) * 4);  // [0] = count, then (first granule, granules) pairs: at most one per tile of csv_parse_regular
   const uint32_t tile_bytes = CT_T;  // csv_parse_regular's tile: seven granules
   const int64_t rtiles = (int64_t)((len + tile_bytes - 1) / tile_bytes);
-  Buf spec_state;
-  if (spec) { spec_state = dalloc((size_t)(2 * rtiles + 2) * 4); TF_HIP(hipMemsetAsync(spec_state->p, 0, (size_t)(2 * rtiles + 2) * 4, st)); }
   CsvParams pp;
   std::memset(&pp, 0, sizeof pp);
   pp.data = data; pp.len = len; pp.row_start = rs; pp.nrows = nrows;
@@ -2473,7 +2282,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   pp.ablate = ablate;
   static const bool force_general = [] { const char *e = std::getenv("TFGPU_CSV_GENERAL"); return e && e[0] == '1'; }();
   pp.gen_n = ptr<uint32_t>(gen); pp.gen_tile = ptr<uint32_t>(gen) + 1; pp.force_general = force_general ? 1 : 0;
-  pp.spec = spec ? ptr<uint32_t>(spec_state) : nullptr; pp.cap_lines = cap_lines;
+  pp.cap_lines = cap_lines;
   Buf ahead_ovf;
   if (ahead) { ahead_ovf = dalloc(4); pp.ovf = ptr<uint32_t>(ahead_ovf); }
   csv_zero_flags<<<1, 64, 0, st>>>(ptr<uint32_t>(fstart_all), fstride, nstr, ptr<uint32_t>(slow), ptr<uint32_t>(gen), ptr<uint32_t>(nerr), pp.ovf);
@@ -2496,7 +2305,11 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   }
   Buf btcols = up(tcols.data(), tcols.size() * sizeof(TCol));
   pp.tcols = ptr<TCol>(btcols);
+#ifdef TF_CSV_ABLATE_BUILD
   static const bool phases = [] { const char *e = std::getenv("TFGPU_CSV_PHASES"); return e && e[0] == '1'; }();
+#else
+  static const bool phases = [] { const char *e = std::getenv("TFGPU_CSV_PHASES"); if (e && e[0] == '1') std::fprintf(stderr, "tfgpu: TFGPU_CSV_PHASES needs the ablate build of tf_csv.hip (tools/build_variant.sh ablate tf_csv.hip -DTF_CSV_ABLATE_BUILD=1); ignored\n"); return false; }();
+#endif
   Buf bphase;
   if (phases) { bphase = dalloc_zero(8 * 8); pp.dbg_phase = ptr<unsigned long long>(bphase); }
   std::vector<CsvRun> runs;
@@ -2508,90 +2321,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   }
   Buf bruns = up(runs.data(), runs.size() * sizeof(CsvRun));
   pp.runs = ptr<CsvRun>(bruns); pp.nruns = (int32_t)runs.size();
-  // ---- the column-lane cell phase: runs of the fast kinds cut into tasks of <= 64 columns (pieces of about 16: four lines per step),
-  //      dealt to the eight waves longest first (TFGPU_CSV_COL_LANES=0: the item form, for A/B runs and as the cross-check) ----
-  // OFF by default.  Measured on the MI355X (gpurun r07s / r07t, 2^20 hits rows, one box): 0.946 ms (pieces of 16 columns), 0.816 (8), 0.825 (4),
-  // 1.23 (32) against the item form's 0.741 — although a step issues a third fewer VALU instructions (≈ 30 against ≈ 48 in the one-to-four-digit
-  // tier).  Group by group (TFGPU_CSV_ABLATE): integers +0.30 ms against +0.17, text +0.48 against +0.15, times +0.10 against +0.065.  A tile holds
-  // 35 lines: a task is a handful of DEPENDENT steps (index reads → window → store) in ONE wave, seven other waves of the workgroup wait at the
-  // barrier behind the longest task, and lines-per-step rounding wastes a quarter of the lanes; the item form deals 58 independent slots round-robin
-  // to all eight waves.  Which lanes hold a column's lines (1 | 2) makes no difference: the stores are not what it waits for.
-  static const int col_lanes = [] { const char *e = std::getenv("TFGPU_CSV_COL_LANES"); return e ? std::atoi(e) : 0; }();  // 0: item form; 1: columns on neighbouring lanes; 2: a column's lines on neighbouring lanes
-  std::vector<CsvTask> tasks; std::vector<int32_t> wave_task(CT_THREADS / 64 + 1, 0);
-  if (col_lanes) {
-    struct Pending { CsvTask k; int cost; };
-    std::vector<Pending> pend;
-    for (auto &r : runs) {
-      if (!(r.kind == CK_INT || r.kind == CK_UINT || r.kind == CK_STR || r.kind == CK_DATE || r.kind == CK_TIMESTAMP)) continue;
-      const int unit = (r.kind == CK_INT || r.kind == CK_UINT) ? (r.width == 8 ? 5 : r.width == 4 ? 3 : 2) : r.kind == CK_STR ? 4 : 6;  // relative cost of a cell
-      static const int piece = [] { const char *e = std::getenv("TFGPU_CSV_COL_PIECE"); return e ? std::max(1, std::min(64, std::atoi(e))) : 16; }();
-      const int pieces = r.ncols <= piece + piece / 3 ? 1 : (r.ncols + piece - 1) / piece;
-      for (int q = 0, at = 0; q < pieces; q++) {
-        const int n = (r.ncols - at + (pieces - q) - 1) / (pieces - q);
-        pend.push_back({CsvTask{r.kind, r.width, r.first + at, n}, n * unit});
-        at += n;
-      }
-    }
-    std::stable_sort(pend.begin(), pend.end(), [](const Pending &a, const Pending &b) { return a.cost > b.cost; });
-    const int nw = CT_THREADS / 64;
-    std::vector<int> load((size_t)nw, 0); std::vector<std::vector<CsvTask>> per((size_t)nw);
-    for (auto &q : pend) { int w = 0; for (int i = 1; i < nw; i++) if (load[(size_t)i] < load[(size_t)w]) w = i; load[(size_t)w] += q.cost; per[(size_t)w].push_back(q.k); }
-    for (int w = 0; w < nw; w++) { wave_task[(size_t)w] = (int32_t)tasks.size(); for (auto &k : per[(size_t)w]) tasks.push_back(k); }
-    wave_task[(size_t)nw] = (int32_t)tasks.size();
-  }
-  if (tasks.empty()) tasks.push_back(CsvTask{0, 0, 0, 1});
-  Buf btasks = up(tasks.data(), std::max<size_t>(tasks.size(), 1) * sizeof(CsvTask)), bwt = up(wave_task.data(), wave_task.size() * 4);
-  pp.tasks = ptr<CsvTask>(btasks); pp.wave_task = ptr<int32_t>(bwt); pp.col_lanes = col_lanes;
   pp.null_checks = (opts->strings_can_be_null || opts->quoted_strings_can_be_null) ? 1 : 0;
-
-  // ---- csv_parse_lanes: the sorted columns cut into 16 contiguous blocks of about equal cost, one per wave; the tile sized so
-  //      that it holds just under 64 lines (or a multiple), within the index's capacity ----
-  // (Measured on the MI355X, profiles/r06c-e: 0.765 ms per 2^20 hits rows against csv_parse_regular's 0.728 — the cells issue a third
-  //  fewer VALU instructions, the byte phases of a 1024-thread workgroup more; both kernels end at 4.2e8 VALU wave-instructions and
-  //  issue VALU 91 % of the time.  It stays selectable, TFGPU_CSV_LANES=1, as the base for the next step)
-  static const bool lanes_on = [] { const char *e = std::getenv("TFGPU_CSV_LANES"); return e && e[0] == '1'; }();
-  bool use_lanes = lanes_on && !rowpath && ncols <= CL_MAXCOLS && nlines > 0;
-  int64_t ltiles = 0;
-  Buf blcols, blwn;
-  if (use_lanes) {
-    auto cost = [](const TCol &t) { return t.field < 0 ? 1 : (t.kind == CK_INT || t.kind == CK_UINT) ? (t.width == 8 ? 3 : 2) : t.kind == CK_STR ? 4 : 8; };
-    int total = 0;
-    for (auto &t : tcols) total += cost(t);
-    std::vector<uint32_t> lcols((size_t)CL_WAVES * 64, 0u), lwn((size_t)CL_WAVES, 0u);
-    int ci = 0, spent = 0;
-    for (int w = 0; w < CL_WAVES && ci < ncols; w++) {
-      // columns for this wave: until its share of the remaining cost is used up (at least one, at most CL_WCOLS, and never
-      // fewer than what the remaining waves can still take)
-      const int share = (total - spent + (CL_WAVES - w) - 1) / (CL_WAVES - w);
-      int got = 0, s = 0;
-      while (ci < ncols && s < CL_WCOLS && (s == 0 || got + cost(tcols[(size_t)ci]) <= share || ncols - ci > (CL_WAVES - w - 1) * CL_WCOLS)) {
-        const TCol &t = tcols[(size_t)ci];
-        const uint64_t o0 = t.p0 ? (uint64_t)((uint8_t *)t.p0 - (uint8_t *)arena->p) : 0, o1 = t.p1 ? (uint64_t)((uint8_t *)t.p1 - (uint8_t *)arena->p) : 0;
-        if ((o0 | o1) & 3) { use_lanes = false; break; }
-        lcols[(size_t)w * 64 + 4 * s] = (uint32_t)(o0 >> 2); lcols[(size_t)w * 64 + 4 * s + 1] = (uint32_t)(o1 >> 2);
-        lcols[(size_t)w * 64 + 4 * s + 2] = (uint32_t)(uint16_t)t.field | ((uint32_t)t.kind << 16) | ((uint32_t)t.width << 24);
-        got += cost(t); s++; ci++;
-      }
-      lwn[(size_t)w] = (uint32_t)s; spent += got;
-    }
-    if (ci < ncols) use_lanes = false;
-    if (use_lanes) {
-      // lines per tile: the largest tile whose expected line count stays under 64 m - margin for some m, and whose expected
-      // field count fits the index; rows longer than ~700 bytes get the largest tile whatever its count
-      const double avg_row = (double)len / (double)nlines, nf_est = std::max<double>(max_field + 1, 1);
-      uint32_t cpt = 1;
-      for (uint32_t c = CL_CPT_MAX; c >= 1; c--) {
-        const double lines = cl_tile(c) / avg_row;
-        if (lines * nf_est <= 0.88 * CL_FCAP && lines <= 0.88 * CL_RCAP) { cpt = c; break; }
-      }
-      pp.tile_cpt = cpt;
-      ltiles = (int64_t)((len + cl_tile(cpt) - 1) / cl_tile(cpt));
-      pp.ntiles = ltiles;
-      pp.arena = (uint8_t *)arena->p;
-      blcols = up(lcols.data(), lcols.size() * 4); blwn = up(lwn.data(), lwn.size() * 4);
-      pp.lcols = ptr<uint32_t>(blcols); pp.lwave_ncols = ptr<uint32_t>(blwn);
-    }
-  }
 
   if (ablate) {  // profiling only: what the skipped phases would have written must not be garbage
     TF_HIP(hipMemsetAsync(lens_all->p, 0, (size_t)std::max(nstr, 1) * (size_t)seg_stride * 4, st));
@@ -2604,15 +2334,10 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     csv_parse_rows<<<blocks_for(nrows, 256), 256, 0, st>>>(pp);
   } else if (nlines) {
     // header lines are parsed by nobody: err[] of the data rows is written by exactly one of the two kernels
-    if (use_lanes) {
-      const int64_t per_xcd = (ltiles + 7) / 8;
-      KernelTimer t("csv_parse_lanes");
-      csv_parse_lanes<<<(unsigned)(per_xcd * 8), CL_THREADS, 0, st>>>(pp);
-    } else {
+    {
       const int64_t per_xcd = (rtiles + 7) / 8;
       KernelTimer t("csv_parse_regular");
-      if (pp.col_lanes) csv_parse_cols<<<(unsigned)(spec ? rtiles : per_xcd * 8), CT_THREADS, 0, st>>>(pp);
-      else csv_parse_regular<<<(unsigned)(spec ? rtiles : per_xcd * 8), CT_THREADS, 0, st>>>(pp);
+      csv_parse_regular<<<(unsigned)(per_xcd * 8), CT_THREADS, 0, st>>>(pp);
     }
     { KernelTimer t("csv_parse_tiles_general"); csv_parse_tiles_general<<<(unsigned)std::min<int64_t>(ntiles + rtiles, 2048), CT_THREADS, 0, st>>>(pp); }
     { KernelTimer t("csv_parse_listed"); csv_parse_listed<<<(unsigned)std::min<int64_t>(blocks_for(slow_cap, 64), 1024), 64, 0, st>>>(pp); }
@@ -2637,12 +2362,12 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   // ---- one read-back: error count, consumed offset, string totals ----
   Buf summary = dalloc((size_t)(2 * nstr + 4) * 4);
   csv_collect<<<1, 64, 0, st>>>(ptr<uint32_t>(nerr), rowpath ? ptr<uint32_t>(row_start) + nlines : pp.last_end, lens_state ? nullptr : ptr<uint32_t>(lens_all),
-                                seg_stride, nrows, nstr, ptr<uint32_t>(fstart_all), fstride, ptr<uint32_t>(summary), pp.spec, rtiles, skip,
-                                ptr<uint32_t>(tile_counts) + (spec ? 0 : ngran), pp.ovf);
+                                seg_stride, nrows, nstr, ptr<uint32_t>(fstart_all), fstride, ptr<uint32_t>(summary), skip,
+                                ptr<uint32_t>(tile_counts) + ngran, pp.ovf);
   const uint32_t *hsum = d2h_u32(summary->p, (size_t)(2 * nstr) + 4);
   tf::sync();
   const uint32_t hnerr = hsum[0], last = hsum[1];
-  if (spec || ahead) {
+  if (ahead) {
     const uint32_t nl_true = hsum[2 + 2 * nstr], overflow = hsum[3 + 2 * nstr];
     // more lines than the buffers hold, fewer than the header skips, or the last '\n' outside the last two tiles: the two-pass way
     if (overflow || nl_true > cap_lines || (int64_t)nl_true < skip || (nl_true && !last)) { *retry = true; return TFGPU_OK; }
@@ -2660,7 +2385,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     uint32_t g = 0, sl = 0;
     d2h(&g, gen->p, 4); d2h(&sl, slow->p, 4);
     tf::sync();
-    std::fprintf(stderr, "tfgpu csv: %s, %lld tiles of %u KiB, %u general pieces; %u lines, %u per-row\n", use_lanes ? "lanes" : "regular", (long long)(use_lanes ? ltiles : rtiles), (use_lanes ? cl_tile(pp.tile_cpt) : tile_bytes) / 1024u, g, nlines, sl);
+    std::fprintf(stderr, "tfgpu csv: regular, %lld tiles of %u KiB, %u general pieces; %u lines, %u per-row\n", (long long)rtiles, tile_bytes / 1024u, g, nlines, sl);
   }
 
   // ---- string payloads: offsets are views into the scanned lens array, or (lens_state) not there yet.  The tile path leaves the
