@@ -1207,6 +1207,35 @@ typedef struct tfgpu_row_meta {
 int tfgpu_apply_meta(tfgpu_plan *const *plans, int nplans, const tfgpu_dbatch *in, const tfgpu_row_meta *meta, tfgpu_dbatch **out,
                      tfgpu_row_error *errs, int64_t errs_cap, int64_t *nerrs);
 
+/* ---- filter_rows_by_ids: a row stays when some text cell starts with an allowed ID (transferia_amd/csrc/tf_byids.hip) -----------
+ * tfgpu_plan_create("filter_rows_by_ids", cfg) takes the Go config (pkg/transformer/registry/filter_rows_by_ids/filter_rows_by_ids.go:
+ * {"tables": {includeTables, excludeTables}, "columns": {includeColumns, excludeColumns}, "allowedIDs": [...]}).  The constructor's
+ * errors are TFGPU_ERR_CONFIG with the Go texts: "unable to create tables filter: ...", "unable to create columns filter: ...",
+ * "list of allowed IDs shouldn't be empty".  Type is filter_rows_by_ids, Description "Row filter by allowed IDs", ResultSchema the input
+ * schema.  An ID list whose bytes or table pass 4 GiB is TFGPU_ERR_UNSUPPORTED by name (the device table has 32-bit offsets).
+ *
+ * Suitable: the table matches in any name variant, and some schema column is of DataType utf8, string or any and matched by the column
+ * filter — or is named `document` with DataType any, whatever the column filter says (the Mongo branch).
+ *
+ * Apply (through tfgpu_apply, tfgpu_apply_meta, in front of a splitter in tfgpu_apply_split, and tfgpu_transformation_*) checks neither
+ * the table nor the kind — Suitable does — and raises no row errors.  A row stays when, walking the batch's TableSchema columns
+ * (tfgpu_batch.schema, or the batch columns when that is NULL) in schema order, some suitable column's value under that name allows it.
+ * The value is AsMap()'s: of several batch columns of one name, the last the row lists.  It allows the row when it is a Go string or
+ * []byte — a TFGPU_R_STRING or TFGPU_R_BYTES cell, or a TFGPU_R_JSON cell whose text is a JSON string, compared by its DECODED bytes
+ * (\" \\ \/ \b \f \n \r \t \uXXXX, surrogate pairs joined, a lone surrogate and bytes that are no UTF-8 read as U+FFFD, as encoding/json
+ * does) — and, for some distinct allowed-ID length L <= len(value), its first L bytes are an allowed ID.  Bytes are compared, not runes.
+ * The text of a TFGPU_R_JSON cell is taken to be valid JSON, as every producer of this ABI writes it: only as many decoded bytes as the longest
+ * allowed ID are read, so a text encoding/json would refuse further on (a raw control byte, an unknown escape, no closing quote) is not noticed.
+ * The allowed ID "" lets every string value through, the empty one too.  Skipped, never a match: nil; an ABSENT cell (AsMap has no entry);
+ * TFGPU_R_JSONNUM (json.Number is no string in the type switch); numbers, times and bools under any DataType; a JSON cell that is an
+ * object, array, number, true, false or null; a schema column the batch does not carry.
+ * Rows without ColumnNames are dropped, by kind and whatever their cells hold: Deletes, TFGPU_K_OTHER, TFGPU_K_SYNCHRONIZE (their
+ * AsMap() is empty).  Updates are judged like Inserts; kind == NULL is all Inserts.
+ * The result is the kept rows in order, as filter_rows hands them on: a selection over the input until somebody reads columns; kinds,
+ * OldKeys, part_id, src_row and the nil / ABSENT bitmaps are carried.  Only the columns the plan reads are materialised.
+ * Whole-call refusals, TFGPU_ERR_UNSUPPORTED by name: a batch whose schema holds a `document` column of DataType any ("Mongo `document`
+ * columns stay with the stock transformer": the reference looks inside a DValue, which a device batch cannot hold); col_order. */
+
 enum {
   TFGPU_QFMT_NATIVE = 1, /* NativeSerializer: "[" + ChangeItem.ToJSONString() + "]", batches joined by ","
                             (native_serializer.go:14-26, native_batcher.go:10-63; MarshalJSON change_item.go:568-616) */

@@ -115,6 +115,10 @@ struct Context {
   struct ConstEntry { uint64_t hash; std::vector<uint8_t> bytes; std::shared_ptr<struct DevMem> mem; uint64_t stamp; };
   std::vector<ConstEntry> consts;
   uint64_t const_clock = 0;
+  // a plan's own device tables on this lane, by the table's id (filter_rows_by_ids' allowed IDs: built with the plan, uploaded on the
+  // lane's first batch and found again after that); the entry used longest ago goes when there are more than 16
+  struct PlanTable { uint64_t id; std::shared_ptr<struct DevMem> mem; uint64_t stamp; };
+  std::vector<PlanTable> plan_tables;
   // tfgpu_csv_parse's sized-ahead form: bytes per line of the last chunk this lane parsed, and that chunk's column count
   double csv_hint_bpl = 0.0;
   int csv_hint_ncols = -1;

@@ -3,6 +3,7 @@
 #include "tf_plan.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -471,6 +472,55 @@ static std::string join_keys(const std::vector<std::string> &v) {
   for (size_t i = 0; i < v.size(); i++) { if (i) o += ", "; o += v[i]; }
   return o;
 }
+// AllowedIDPrefixesByLength (filter_rows_by_ids.go:55-64) as the image tf_byids.hpp describes: built once, with the plan
+static std::shared_ptr<const ByIdsTable> build_byids_table(const std::vector<std::string> &allowed) {
+  static std::atomic<uint64_t> next_id{1};
+  std::vector<std::string> ids(allowed);
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());  // a set: duplicates are harmless
+  auto t = std::make_shared<ByIdsTable>();
+  t->id = next_id.fetch_add(1);
+  std::vector<uint32_t> lens;
+  uint64_t nbytes = 0;
+  for (auto &s : ids) {
+    if (s.size() >= 0xFFFFFFFFull) throw Error(TFGPU_ERR_UNSUPPORTED, "filter_rows_by_ids: an allowed ID of 4 GiB or more does not fit the device table's 32-bit lengths");
+    lens.push_back((uint32_t)s.size());
+    nbytes += s.size();
+  }
+  std::sort(lens.begin(), lens.end());
+  lens.erase(std::unique(lens.begin(), lens.end()), lens.end());
+  uint64_t cap = 4;
+  while (cap < 2 * (uint64_t)ids.size()) cap *= 2;
+  const uint64_t words = lens.size() + 3 * cap + (nbytes + 3) / 4;
+  if (words * 4 > 0xFFFFFFFFull)
+    throw Error(TFGPU_ERR_UNSUPPORTED, "filter_rows_by_ids: " + std::to_string(ids.size()) + " allowed IDs of " + std::to_string(nbytes) +
+                                           " bytes need a device table past 4 GiB, which its 32-bit offsets do not address; keep this transformer on the host");
+  t->nlen = (uint32_t)lens.size(); t->cap = (uint32_t)cap;
+  t->image.assign((size_t)words, 0u);
+  std::copy(lens.begin(), lens.end(), t->image.begin());
+  uint32_t *slots = t->image.data() + t->nlen;
+  for (uint64_t s = 0; s < cap; s++) slots[3 * s + 2] = BYIDS_EMPTY;
+  uint8_t *bytes = reinterpret_cast<uint8_t *>(slots + 3 * cap);
+  uint32_t off = 0;
+  const uint32_t mask = (uint32_t)cap - 1;
+  for (auto &s : ids) {
+    uint32_t h = BYIDS_FNV_INIT;
+    for (unsigned char c : s) h = byids_step(h, c);
+    const uint32_t key = byids_key(h, (uint32_t)s.size());
+    uint32_t at = byids_home(key, mask);
+    while (slots[3 * at + 2] != BYIDS_EMPTY) at = (at + 1) & mask;
+    slots[3 * at] = key; slots[3 * at + 1] = off; slots[3 * at + 2] = (uint32_t)s.size();
+    if (!s.empty()) std::memcpy(bytes + off, s.data(), s.size());
+    off += (uint32_t)s.size();
+  }
+  return t;
+}
+
+bool byids_mongo_document(const std::string &name, int dtype) { return name == "document" && dtype == TFGPU_T_ANY; }  // filter_rows_by_ids.go:186-188
+bool byids_column_suitable(const tfgpu_plan &p, const std::string &name, int dtype) {                                // :190-196
+  return (dtype == TFGPU_T_UTF8 || dtype == TFGPU_T_BYTES || dtype == TFGPU_T_ANY) && p.columns.match(name);
+}
+
 std::unique_ptr<tfgpu_plan> make_plan(const std::string &type_name, const std::string &config_json) {
   Json cfg = Json::parse(config_json.empty() ? "{}" : config_json);
   auto p = std::make_unique<tfgpu_plan>();
@@ -591,10 +641,19 @@ std::unique_ptr<tfgpu_plan> make_plan(const std::string &type_name, const std::s
     if (cfg.flag("shouldUpdateOldKeys"))
       throw Error(TFGPU_ERR_UNSUPPORTED, "raw_doc_grouper shouldUpdateOldKeys=true gives every Update row its own OldKeys name list (processUpdateItem appends the additional keys row by "
                                          "row: ragged OldKeys), which a columnar batch cannot express; not a device transform");
+  } else if (type_name == "filter_rows_by_ids") {  // filter_rows_by_ids/filter_rows_by_ids.go:42-72
+    p->kind = PK_FILTER_ROWS_BY_IDS;
+    try { p->tables = tables_of(cfg); }
+    catch (const Error &e) { if (e.code == TFGPU_ERR_CONFIG) cfg_error(std::string("unable to create tables filter: ") + e.what()); throw; }
+    try { p->columns = columns_of(cfg); }
+    catch (const Error &e) { if (e.code == TFGPU_ERR_CONFIG) cfg_error(std::string("unable to create columns filter: ") + e.what()); throw; }
+    const std::vector<std::string> ids = cfg.strings("allowedIDs");
+    if (ids.empty()) cfg_error("list of allowed IDs shouldn't be empty");
+    p->byids = build_byids_table(ids);
   } else if (type_name == "lambda" || type_name == "dbt" || type_name == "logger" || type_name == "yt_dict_transformer" ||
              type_name == "raw_cdc_doc_grouper" || type_name == "number_to_float_transformer" ||
              type_name == "problem_item_detector" || type_name == "batch_splitter" || type_name == "filter_strm_access_log" || type_name == "jsonparser" ||
-             type_name == "filter_rows_by_ids" || type_name == "mongo_pk_extender") {
+             type_name == "mongo_pk_extender") {
     // registered in the reference (pkg/transformer/registry/*), outside the device subset (out of scope)
     throw Error(TFGPU_ERR_UNSUPPORTED, "transformer type " + type_name + " has no device plan: keep it on the host");
   } else {
@@ -669,6 +728,13 @@ bool plan_suitable(const tfgpu_plan &p, const std::string &ns, const std::string
       for (auto *list : {&p.rd_keys, &p.rd_fields}) for (auto &n : *list) if (!rawdoc_special(n) && !in_schema(n)) return false;
       return true;
     }
+    case PK_FILTER_ROWS_BY_IDS:  // filter_rows_by_ids.go:170-184: a `document` column of `any` counts whatever the column filter says
+      if (!p.tables.match_table(ns, name)) return false;
+      for (int i = 0; i < s.ncols; i++) {
+        const std::string cn = s.cols[i].name ? s.cols[i].name : "";
+        if (byids_column_suitable(p, cn, s.cols[i].dtype) || byids_mongo_document(cn, s.cols[i].dtype)) return true;
+      }
+      return false;
     case PK_REGEX_REPLACE: return p.tables.match(name);  // transformer.go:64-66: the table's name alone, no namespace variants
     case PK_TO_DATETIME:  // to_datetime.go:63-76
       if (!p.tables.match_table(ns, name)) return false;
@@ -719,6 +785,7 @@ std::string plan_description(const tfgpu_plan &p) {
       return "Table splitter for tables=(include: " + trim_and_more(join(p.tables.include_src, "|"), 100) + ", exclude: " + trim_and_more(join(p.tables.exclude_src, "|"), 100) +
              "); columns=(" + trim_and_more(join(p.tables.exclude_src, ","), 100) + "); splitter=" + p.splitter;
     case PK_RAW_DOC_GROUPER: return "Return item as primary keys " + join(p.rd_keys, ", ") + " and json, containing the rest";  // raw_doc_grouper.go:154-156
+    case PK_FILTER_ROWS_BY_IDS: return "Row filter by allowed IDs";  // filter_rows_by_ids.go:202-204
     case PK_REPLACE_PK: return "Replace primary keys to: " + join_keys(p.new_keys) + " ";
     case PK_SHARDER:
       if (p.columns.empty()) return "Transform to shard tables by field values";

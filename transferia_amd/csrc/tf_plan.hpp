@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "tf_common.hpp"
+#include "tf_byids.hpp"
 
 namespace tf {
 
@@ -58,7 +59,7 @@ std::vector<FTerm> parse_filter(const std::string &src);  // throws Error(TFGPU_
 
 }  // namespace tf
 
-enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL, PK_REGEX_REPLACE, PK_TABLE_SPLITTER, PK_RAW_DOC_GROUPER };
+enum PlanKind { PK_MASK, PK_RENAME, PK_FILTER_COLUMNS, PK_SKIP_EVENTS, PK_FILTER_ROWS, PK_TO_STRING, PK_TO_DATETIME, PK_SHARDER, PK_REPLACE_PK, PK_SQL, PK_REGEX_REPLACE, PK_TABLE_SPLITTER, PK_RAW_DOC_GROUPER, PK_FILTER_ROWS_BY_IDS };
 
 namespace tf {
 // ---- `sql` transformer, device subset (tf_sql.cpp) ----------------------------------------------------------------------
@@ -137,6 +138,8 @@ struct tfgpu_plan {
   std::string splitter;                 // as configured: empty means "/" when a name is built, Description prints it as it is
   // raw_doc_grouper (tf_rawdoc.hip)
   std::vector<std::string> rd_keys, rd_fields;  // `keys` as configured; `fields` with etl_updated_at / doc appended where neither list names them (NewRawDocGroupTransformer)
+  // filter_rows_by_ids (tf_byids.hip): the allowed IDs as the device tables, built once here; `columns` is its column filter
+  std::shared_ptr<const tf::ByIdsTable> byids;
   // replace_primary_key
   std::vector<std::string> new_keys;
   bool is_new_key(const std::string &n) const {
@@ -180,6 +183,9 @@ std::unique_ptr<tfgpu_dbatch> apply_mask(const tfgpu_plan &p, const tfgpu_dbatch
 std::unique_ptr<tfgpu_dbatch> apply_sql(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);
 std::unique_ptr<tfgpu_dbatch> apply_regex_replace(const tfgpu_plan &p, const tfgpu_dbatch &in);
 std::unique_ptr<tfgpu_dbatch> apply_raw_doc(const tfgpu_plan &p, const tfgpu_dbatch &in, ApplyCtx &ax);  // tf_rawdoc.hip
+std::unique_ptr<tfgpu_dbatch> apply_filter_by_ids(const tfgpu_plan &p, const tfgpu_dbatch &in);         // tf_byids.hip
+bool byids_column_suitable(const tfgpu_plan &p, const std::string &name, int dtype);                    // checkColumnSuitable
+bool byids_mongo_document(const std::string &name, int dtype);                                          // isMongoDocumentColumn
 bool rawdoc_special(const std::string &name);                                                            // etl_updated_at / doc (rawDocFields)
 const tfgpu_plan *chain_raw_doc(tfgpu_plan *const *plans, int nplans);                                  // the chain's first raw_doc_grouper, or null
 // plans[0 .. nplans) over a snapshot of `in`, the loop of tfgpu_apply (tf_api.hip; the caller holds the lane's mutex): for tfgpu_apply_split (tf_tablesplit.hip)

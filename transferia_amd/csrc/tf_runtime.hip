@@ -88,6 +88,7 @@ static void destroy_lane(std::unique_ptr<Context> &c) {
   if (c->dense_event) hipEventDestroy(c->dense_event);  // (the stream was synchronised above: every gather it stood behind is complete)
   c->pow10tab.reset();
   c->consts.clear();
+  c->plan_tables.clear();
   c->blocks.trim();
   if (c->pin_base) hipHostFree(c->pin_base);
   hipStreamDestroy(c->stream);

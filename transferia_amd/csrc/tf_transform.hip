@@ -1,6 +1,6 @@
 // tf_transform.hip — device kernels behind abstract.Transformer.Apply for the
 // row transformers of SURVEY.md §8a (a6–a13), plus the apply dispatcher (mask_field: tf_mask.hip, sql: tf_sqleval.hip,
-// regex_replace_transformer: tf_regex.hip; raw_doc_grouper: tf_rawdoc.hip; the row machinery under all of them: tf_rows.hip).
+// regex_replace_transformer: tf_regex.hip; raw_doc_grouper: tf_rawdoc.hip; filter_rows_by_ids: tf_byids.hip; the row machinery under all of them: tf_rows.hip).
 //
 // All kernels are byte/row kernels: one lane per row, column-major (Arrow)
 // buffers so that neighbouring lanes touch neighbouring addresses.  None of
@@ -701,6 +701,8 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
     if (in.col_order)
       throw Error(TFGPU_ERR_UNSUPPORTED, "raw_doc_grouper: the batch's rows carry their own ColumnNames order (col_order: a collapsed batch), which the result's column list does not carry");
   }
+  if (p.kind == PK_FILTER_ROWS_BY_IDS && in.col_order)  // (ABSENT cells it reads itself: AsMap has no entry for them)
+    throw Error(TFGPU_ERR_UNSUPPORTED, "filter_rows_by_ids: the batch's rows carry their own ColumnNames order (col_order: a collapsed batch); such rows stay with the stock transformer");
   if (p.kind == PK_SQL || p.kind == PK_REGEX_REPLACE || (in.col_order && p.kind != PK_SHARDER)) refuse_absent(in);
   // `in` is the caller's OWN copy of the handle it was given (tfgpu_apply and push_run take it with snapshot(), under the transition's lock): nobody
   // else changes it.  A copy taken after another lane made the handle dense carries that lane's event: this lane's stream waits for it here.
@@ -719,6 +721,7 @@ std::unique_ptr<tfgpu_dbatch> apply_plan(const tfgpu_plan &p, const tfgpu_dbatch
     case PK_SQL: return apply_sql(p, in, ax);
     case PK_REGEX_REPLACE: return apply_regex_replace(p, in);
     case PK_RAW_DOC_GROUPER: return apply_raw_doc(p, in, ax);
+    case PK_FILTER_ROWS_BY_IDS: return apply_filter_by_ids(p, in);
     case PK_TABLE_SPLITTER: break;  // (refused above)
   }
   throw Error(TFGPU_ERR_INVALID, "unknown plan kind");
