@@ -237,8 +237,8 @@ static int lex_one(const char *s, size_t n, ftoken *t) {
     }
   }
   if (s[0] == '(' || s[0] == ')' || s[0] == ',') { t->type = TK_PUNCT; t->n = 1; return 0; }
-  if (s[0] == ' ' || s[0] == '\t' || s[0] == '\n' || s[0] == '\r' || s[0] == '\f' || s[0] == '\v') {
-    size_t i = 1; while (i < n && (s[i] == ' ' || s[i] == '\t' || s[i] == '\n' || s[i] == '\r' || s[i] == '\f' || s[i] == '\v')) i++;
+  if (s[0] == ' ' || s[0] == '\t' || s[0] == '\n' || s[0] == '\r' || s[0] == '\f') { /* regexp's \s: no vertical tab */
+    size_t i = 1; while (i < n && (s[i] == ' ' || s[i] == '\t' || s[i] == '\n' || s[i] == '\r' || s[i] == '\f')) i++;
     t->type = TK_WS; t->n = i; return 0;
   }
   return 1;
@@ -273,6 +273,7 @@ static char *go_unquote(const char *s, size_t n, size_t *olen, int *bad) {
         if (i + (size_t)nd > n) { *bad = 1; break; }
         for (int k = 0; k < nd; k++) { char h = s[i + (size_t)k]; int d = isdig(h) ? h - '0' : (h >= 'a' && h <= 'f') ? h - 'a' + 10 : (h >= 'A' && h <= 'F') ? h - 'A' + 10 : -1; if (d < 0) { *bad = 1; d = 0; } v = v * 16 + (unsigned)d; }
         i += (size_t)nd;
+        if (e != 'x' && (v > 0x10FFFF || (v >= 0xD800 && v < 0xE000))) { *bad = 1; break; } /* strconv.UnquoteChar: !utf8.ValidRune */
         if (e == 'x') o[w++] = (char)v;
         else { if (v < 0x80) o[w++] = (char)v; else if (v < 0x800) { o[w++] = (char)(0xC0 | v >> 6); o[w++] = (char)(0x80 | (v & 0x3F)); } else if (v < 0x10000) { o[w++] = (char)(0xE0 | v >> 12); o[w++] = (char)(0x80 | ((v >> 6) & 0x3F)); o[w++] = (char)(0x80 | (v & 0x3F)); } else { o[w++] = (char)(0xF0 | v >> 18); o[w++] = (char)(0x80 | ((v >> 12) & 0x3F)); o[w++] = (char)(0x80 | ((v >> 6) & 0x3F)); o[w++] = (char)(0x80 | (v & 0x3F)); } }
         break;
@@ -823,7 +824,27 @@ static int string_to_time(const char *s, size_t n, int64_t *sec, int32_t *nsec) 
 static int64_t unix_micro(int64_t sec, int32_t nsec) { return sec * 1000000 + nsec / 1000; }
 
 /* matchValue filter_rows.go:180-365.  returns 1/0 match, or -code on error */
+static int match_value_go(const ora_value *v1, const fterm *tm);
+/* An `any` cell is to matchValue what encoding/json decoded from its text into an interface{}: a string (checkColumnSuitable admits TypeAny for
+ * string constants, filter_rows.go:505-509), a float64, a bool.  A map or a slice meets no case of its switches ("Unsupported type pair", and
+ * not nil under a NULL term); so does, here, a text that does not parse or is `null`. */
 static int match_value(const ora_value *v1, const fterm *tm) {
+  if (v1->kind != OV_JSON) return match_value_go(v1, tm);
+  char e[64]; char *z = dupn(v1->s, v1->slen);
+  jnode *n = jn_parse(z, e, sizeof e);
+  free(z);
+  ora_value d; memset(&d, 0, sizeof d); d.kind = OV_JSON;
+  if (n) switch (n->type) {
+    case JN_STR: d.kind = OV_STRING; d.s = n->str; d.slen = n->slen; break;
+    case JN_NUM: d.kind = OV_F64; d.v.f64 = n->num; break;
+    case JN_BOOL: d.kind = OV_BOOL; d.v.b = n->b; break;
+    default: break;
+  }
+  int r = match_value_go(n ? &d : v1, tm);
+  if (n) jn_free(n);
+  return r;
+}
+static int match_value_go(const ora_value *v1, const fterm *tm) {
   const fvalue *v2 = &tm->val; int op = tm->op;
   int is_set = (op == OP_IN || op == OP_NOTIN);
   int isInt1 = 0, isFloat1 = 0; int64_t int1 = 0; double float1 = 0;

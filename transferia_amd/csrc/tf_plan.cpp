@@ -177,6 +177,7 @@ enum Tk { T_OP, T_STR, T_DT, T_ID, T_FLOAT, T_INT, T_PUNCT, T_WS, T_EOF };
 struct Tok { Tk t; std::string s; };
 bool dg(char c) { return c >= '0' && c <= '9'; }
 bool al(char c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); }
+bool go_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\f' || c == '\r'; }  // regexp's \s: no vertical tab (isspace takes one)
 
 std::vector<Tok> lex(const std::string &in) {
   std::vector<Tok> out;
@@ -222,7 +223,7 @@ std::vector<Tok> lex(const std::string &in) {
         else t = T_INT;
         len = j;
       } else if (p[0] == '(' || p[0] == ')' || p[0] == ',') { t = T_PUNCT; len = 1; }
-      else if (std::isspace((unsigned char)p[0])) { size_t j = 1; while (j < r && std::isspace((unsigned char)p[j])) j++; t = T_WS; len = j; }
+      else if (go_space(p[0])) { size_t j = 1; while (j < r && go_space(p[j])) j++; t = T_WS; len = j; }
       else cfg_error("filter: invalid token at position " + std::to_string(i));
     }
     out.push_back({t, in.substr(i, len)});
@@ -255,8 +256,11 @@ std::string go_unquote(const std::string &tok) {
       case 'r': o += '\r'; break; case 't': o += '\t'; break; case 'v': o += '\v'; break; case '\\': o += '\\'; break;
       case '\'': case '"': if (e != q) cfg_error("filter: invalid escape"); o += e; break;
       case 'x': o += (char)hexv(2); break;
-      case 'u': JP::put_utf8(o, hexv(4)); break;
-      case 'U': JP::put_utf8(o, hexv(8)); break;
+      case 'u': case 'U': {
+        unsigned v = hexv(e == 'u' ? 4 : 8);
+        if (v > 0x10FFFF || (v >= 0xD800 && v < 0xE000)) cfg_error("filter: invalid escape");  // strconv.UnquoteChar: !utf8.ValidRune
+        JP::put_utf8(o, v); break;
+      }
       default:
         if (e >= '0' && e <= '7') {
           if (i + 2 > s.size()) cfg_error("filter: invalid escape");
@@ -302,6 +306,7 @@ int64_t parse_filter_time(const std::string &v) {
         if (k - b != 2) cfg_error("filter: cannot parse datetime " + v);
         int hh = num(b, 2), mm = 0;
         if (k < v.size() && v[k] == ':') { k++; size_t c = k; while (k < v.size() && dg(v[k])) k++; if (k - c != 2) cfg_error("filter: cannot parse datetime " + v); mm = num(c, 2); }
+        if (hh > 24 || mm > 60) cfg_error("filter: cannot parse datetime " + v);  // time.Parse: "time zone offset hour" / "minute" out of range
         off = sign * (hh * 3600 + mm * 60);
       }
     }
@@ -359,7 +364,7 @@ void scalar_into(P &p, FTerm &term, bool in_list) {
   switch (ty) {
     case FV_STRING: term.strs.push_back(go_unquote(t.s)); break;
     case FV_TIME: term.ints.push_back(parse_filter_time(t.s)); break;
-    case FV_FLOAT: term.floats.push_back(std::strtod(t.s.c_str(), nullptr)); break;
+    case FV_FLOAT: { double f = std::strtod(t.s.c_str(), nullptr); if (std::isinf(f)) cfg_error("filter: value out of range"); term.floats.push_back(f); break; }  // strconv.ParseFloat's ErrRange
     case FV_INT: { int64_t v; if (!parse_i64(t.s, v)) cfg_error("filter: value out of range"); term.ints.push_back(v); break; }
     case FV_BOOL: term.ints.push_back(kw(t, "TRUE") ? 1 : 0); break;
     case FV_NULL: term.ints.push_back(0); break;

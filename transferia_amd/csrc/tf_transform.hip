@@ -92,14 +92,15 @@ __device__ __forceinline__ bool bytes_contains(const uint8_t *h, uint32_t hn, co
 // time.Parse over the layouts of stringToTime (filter_rows/util.go:15-39) that
 // are fixed-shape numeric: "2006-01-02", "2006-01-02 15:04:05", "2006-01-02T15:04:05",
 // RFC3339 / RFC3339Nano.  Returns 1 ok, 0 = does not look like any of them
-// (the row is then handed back to the host path).
+// (the row is then handed back to the host path), 2 = one of these shapes with a field out of range (Feb 30, 24:00, +25:00): its own
+// layout reports the range, every other layout of stringToTime stops at its first punctuation mark, so no layout parses it.
 __device__ __forceinline__ bool is_dg(uint8_t c) { return c >= '0' && c <= '9'; }
 __device__ int parse_time_subset(const uint8_t *s, uint32_t n, int64_t *sec, int32_t *nsec) {
   if (n < 10) return 0;
   if (!(is_dg(s[0]) && is_dg(s[1]) && is_dg(s[2]) && is_dg(s[3]) && s[4] == '-' && is_dg(s[5]) && is_dg(s[6]) && s[7] == '-' && is_dg(s[8]) && is_dg(s[9]))) return 0;
   int64_t y = (s[0] - '0') * 1000 + (s[1] - '0') * 100 + (s[2] - '0') * 10 + (s[3] - '0');
   int mo = (s[5] - '0') * 10 + (s[6] - '0'), d = (s[8] - '0') * 10 + (s[9] - '0');
-  int h = 0, mi = 0, se = 0; int64_t ns = 0; int off = 0;
+  int h = 0, mi = 0, se = 0; int64_t ns = 0; int off = 0; bool zone_range = false;
   uint32_t k = 10;
   if (n > 10) {
     if (!(s[10] == 'T' || s[10] == ' ')) return 0;
@@ -118,14 +119,14 @@ __device__ int parse_time_subset(const uint8_t *s, uint32_t n, int64_t *sec, int
       if (s[k] == 'Z') k++;
       else if ((s[k] == '+' || s[k] == '-') && k + 6 <= n && is_dg(s[k + 1]) && is_dg(s[k + 2]) && s[k + 3] == ':' && is_dg(s[k + 4]) && is_dg(s[k + 5])) {
         int hh = (s[k + 1] - '0') * 10 + (s[k + 2] - '0'), mm = (s[k + 4] - '0') * 10 + (s[k + 5] - '0');
-        if (hh > 24 || mm > 60) return 0;
+        zone_range = hh > 24 || mm > 60;
         off = (s[k] == '-' ? -1 : 1) * (hh * 3600 + mm * 60);
         k += 6;
       } else return 0;
       if (k != n) return 0;
     }
   }
-  if (mo < 1 || mo > 12 || d < 1 || d > dev::days_in_month(mo, y) || h > 23 || mi > 59 || se > 59) return 0;
+  if (zone_range || mo < 1 || mo > 12 || d < 1 || d > dev::days_in_month(mo, y) || h > 23 || mi > 59 || se > 59) return 2;
   *sec = dev::days_from_civil(y, mo, d) * 86400 + h * 3600 + mi * 60 + se - off;
   *nsec = (int32_t)ns;
   return 1;
@@ -152,6 +153,14 @@ __device__ int match_value(const FilterParams &p, const DTerm &t, int64_t r) {
       case TFGPU_R_FLOAT64: float1 = ((const double *)c.values)[r]; isFloat1 = true; break;
       case TFGPU_R_BOOL: float1 = ((const uint8_t *)c.values)[r] ? 1.0 : 0.0; isFloat1 = true; break;
       case TFGPU_R_STRING: case TFGPU_R_JSONNUM: maybeFloat = true; break;  // strconv.ParseFloat of text
+      case TFGPU_R_JSON: {
+        // an `any` cell is the value encoding/json decoded from its text.  A map or a slice meets no case below ("Unsupported type pair"); a string,
+        // a number or a bool is compared as such by the reference (checkColumnSuitable admits TypeAny for string constants): the host path's to decode
+        if (t.vtype == FV_NULL) break;
+        const uint8_t *a = c.data + c.offsets[r]; uint32_t an = c.offsets[r + 1] - c.offsets[r], k = 0;
+        while (k < an && (a[k] == ' ' || a[k] == '\t' || a[k] == '\n' || a[k] == '\r')) k++;
+        return (k < an && (a[k] == '{' || a[k] == '[')) ? -TFGPU_ROW_TYPE_PAIR : -TFGPU_ROW_HOST_FALLBACK;
+      }
     }
   } else { float1 = 0; isFloat1 = true; }  // cast.ToFloat64E(nil) == 0
   int res;
@@ -164,7 +173,11 @@ __device__ int match_value(const FilterParams &p, const DTerm &t, int64_t r) {
       if (maybeFloat) return -TFGPU_ROW_HOST_FALLBACK;
       if (isFloat1) {
         if (is_set) {
-          if (trunc(float1) == float1) { int64_t iv = (int64_t)float1; bool f = false; for (int i = 0; i < t.nvals; i++) f = f || p.ints[t.ioff + i] == iv; return t.op == F_IN ? f : !f; }
+          if (trunc(float1) == float1) {
+            // Go leaves int64(float1) outside the int64 range to the implementation (amd64: MinInt64, arm64: saturated; this device: neither): the host path's to answer
+            if (!(float1 >= -0x1p63 && float1 < 0x1p63)) return -TFGPU_ROW_HOST_FALLBACK;
+            int64_t iv = (int64_t)float1; bool f = false; for (int i = 0; i < t.nvals; i++) f = f || p.ints[t.ioff + i] == iv; return t.op == F_IN ? f : !f;
+          }
           return 0;
         }
         res = cmp_op_f(float1, (double)p.ints[t.ioff], t.op); return res < 0 ? -TFGPU_ROW_TYPE_PAIR : res;
@@ -202,7 +215,9 @@ __device__ int match_value(const FilterParams &p, const DTerm &t, int64_t r) {
       if (valid && c.repr == TFGPU_R_TIME) { us1 = ((const int64_t *)c.values)[r] * 1000000 + (c.nanos ? c.nanos[r] : 0) / 1000; have = true; }
       else if (valid && c.repr == TFGPU_R_STRING) {
         int64_t s; int32_t ns;
-        if (!parse_time_subset(c.data + c.offsets[r], c.offsets[r + 1] - c.offsets[r], &s, &ns)) return -TFGPU_ROW_HOST_FALLBACK;
+        int shape = parse_time_subset(c.data + c.offsets[r], c.offsets[r + 1] - c.offsets[r], &s, &ns);
+        if (shape == 0) return -TFGPU_ROW_HOST_FALLBACK;
+        if (shape == 2) break;  // stringToTime finds no layout: "Unsupported type pair"
         us1 = s * 1000000 + ns / 1000; have = true;
       }
       if (have) {

@@ -38,7 +38,7 @@ def raw_column_messages(batch: lib.DeviceBatch, column_name: str, schema: Option
     starts = (C.c_uint32 * (cap + 1))()
     out, n = C.c_void_p(), C.c_int64(0)
     cs = schema.to_c() if schema is not None else None
-    lib._check(lib.load().tfgpu_queue_raw_column(batch._h, column_name.encode(), C.byref(cs) if cs is not None else None, C.byref(out), starts, cap, C.byref(n)))
+    lib._check(lib.load().tfgpu_queue_raw_column(batch._h, column_name.encode(), C.byref(cs) if cs is not None else None, C.byref(out), starts, C.c_int64(cap), C.byref(n)))
     return _cut(lib.DeviceBuffer(out), starts, n.value)
 
 
@@ -49,7 +49,7 @@ def mirror_messages(batch: lib.DeviceBatch, schema: Optional[abi.Schema] = None)
     nil = (C.c_uint8 * cap)()
     v, k, n = C.c_void_p(), C.c_void_p(), C.c_int64(0)
     cs = schema.to_c() if schema is not None else None
-    lib._check(lib.load().tfgpu_queue_mirror(batch._h, C.byref(cs) if cs is not None else None, C.byref(v), vs, C.byref(k), ks, nil, cap, C.byref(n)))
+    lib._check(lib.load().tfgpu_queue_mirror(batch._h, C.byref(cs) if cs is not None else None, C.byref(v), vs, C.byref(k), ks, nil, C.c_int64(cap), C.byref(n)))   # (an int64_t passed on the stack: a bare Python int fills only its low half)
     vals, keys = _cut(lib.DeviceBuffer(v), vs, n.value), _cut(lib.DeviceBuffer(k), ks, n.value)
     return [(None if nil[i] else keys[i], vals[i]) for i in range(n.value)]
 
@@ -61,7 +61,7 @@ def part_groups(batch: lib.DeviceBatch):
     order = np.zeros(max(n, 1), np.int32)
     cap = max(n, 1)
     rows, ids, ng = (C.c_int64 * cap)(), (C.c_uint32 * cap)(), C.c_int64(0)
-    lib._check(lib.load().tfgpu_queue_part_groups(batch._h, order.ctypes.data_as(C.POINTER(C.c_int32)), rows, ids, cap, C.byref(ng)))
+    lib._check(lib.load().tfgpu_queue_part_groups(batch._h, order.ctypes.data_as(C.POINTER(C.c_int32)), rows, ids, C.c_int64(cap), C.byref(ng)))
     has = batch.view().part_id is not None and bool(batch.view().part_id)
     return order[:n], [int(rows[g]) for g in range(ng.value)], [str(int(ids[g])) if has else "" for g in range(ng.value)]
 
@@ -70,7 +70,7 @@ def kafka_hash_partition(key: Optional[bytes], npartitions: int) -> Optional[int
     if key is None:
         return None
     lib.load().tfgpu_kafka_hash_partition.restype = C.c_int32
-    return int(lib.load().tfgpu_kafka_hash_partition(key, len(key), npartitions))
+    return int(lib.load().tfgpu_kafka_hash_partition(key, C.c_int64(len(key)), npartitions))
 
 
 def kafka_partitions(batch: lib.DeviceBatch, key_column: str, npartitions: int) -> List[Optional[int]]:
