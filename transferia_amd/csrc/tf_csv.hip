@@ -1130,8 +1130,11 @@ struct RegCell { bool on; uint32_t col, jj, fs, fend; int32_t r; };
 // (column offset, line) pair comes from one division, the following ones from adding 512 / nr and 512 % nr with one carry.
 struct ItemIter { uint32_t it, oi, jj; };
 __device__ __forceinline__ ItemIter item_first(const RegTile &t, uint32_t it) {
-  // it / nr through the float reciprocal (rounded down, so the quotient is never too large; it < 2^24): all full-rate ops
-  uint32_t oi = (uint32_t)(__uint2float_rz(it) * t.inv_nr);
+  // it / nr through the float reciprocal (inv_nr is a hair below 1 / nr, so the quotient is never too large): all full-rate ops.
+  // An item number is below CR_LCOLS * CT_RCAP < 2^24, which a float holds exactly: the plain conversion is one v_cvt_f32_u32,
+  // where a conversion with a stated rounding mode is a dozen instructions.
+  static_assert((uint64_t)CR_LCOLS * CT_RCAP < (1u << 24), "item numbers must be exact as floats");
+  uint32_t oi = (uint32_t)((float)it * t.inv_nr);
   uint32_t jj = it - __umul24(oi, t.nr);
   if (jj >= t.nr) { oi++; jj -= t.nr; }
   return ItemIter{it, oi, jj};
@@ -1260,15 +1263,39 @@ template <int KIND, int W> __device__ __forceinline__ void reg_cells_int(const R
 
 __device__ __forceinline__ void reg_str_body(const RegTile &t, const RegCell &c, uint32_t *const lens, uint32_t *const fstart) {
   const uint32_t n = c.fend - c.fs;
-  const uint32_t c_first = t.sb[c.fs], c_last = t.sb[c.fend - 1];
+  const uint32_t c_first = t.sb[c.fs];
+  // the field's last four bytes [fend - 4, fend) from one aligned word pair: the last byte on top, what precedes it below
+  // (bytes in front of a short field are the neighbouring field's, or the 32 bytes in front of the tile: readable either way)
+  const uint32_t *w4 = reinterpret_cast<const uint32_t *>(t.sb + (int)((c.fend & ~3u) - 4u));
+  const uint32_t tail = __builtin_amdgcn_alignbyte(w4[1], w4[0], c.fend), c_last = tail >> 24;
   const uint32_t qn = quotes_in(t, c.fs, c.fend);  // quote characters in the field
-  // straight path: empty; no quote inside and printable ASCII (not a space, not DEL) at both ends; or enclosed in the
-  // only two quotes it holds ("…": unquote, nothing to collapse)
-  const bool plain = qn == 0 && c_first - 0x21u < 0x5Eu && c_last - 0x21u < 0x5Eu;
-  const bool quoted = qn == 2 && c_first == t.quote && c_last == t.quote;  // (n >= 2 then: two quote characters are in it)
-  if (wave_all(n == 0 || plain || quoted || !c.on)) {
-    const uint32_t q1 = quoted ? 1u : 0u;
-    if (c.on) { lens[c.r] = n - 2u * q1; fstart[c.r] = t.g0 + c.fs + q1; }
+  // straight path: every cell whose text is a byte range with nothing to trim — empty; no quote inside and neither end a
+  // rune sanitizeElement could trim; or enclosed in quotes ("…": unquote, and count the "" pairs inside if it holds more
+  // than its two).  The test of the ends is a branch-free superset of !starts_plain / !ends_plain: ASCII must be printable
+  // and no space; a first byte >= 0x80 must not be C2 / E1 / E2 / E3 (the lead bytes of every Unicode space); a last byte
+  // >= 0x80 must be a lead byte (malformed, never a space) or have neither C2 right in front of it nor E1 / E2 / E3 two in
+  // front (looked at even where that byte is outside the cell).  A false alarm only sends the slot to the general code below.
+  // (bitwise on purpose: with && / || the compiler builds exec-mask branches around the later terms)
+  const bool first_ok = (c_first - 0x21u < 0x5Eu) | ((c_first >= 0x80u) & (c_first != 0xC2u) & (c_first - 0xE1u >= 3u));
+  const bool last_ok = (c_last - 0x21u < 0x5Eu) | (c_last >= 0xC0u) |
+                       ((c_last >= 0x80u) & ((tail & 0x00FF0000u) != 0x00C20000u) & ((tail & 0x0000FF00u) - 0xE100u >= 0x300u));
+  const bool plain = (qn == 0) & first_ok & last_ok;
+  const bool enclosed = (n - 2u < 0x7FFEu) & (c_first == t.quote) & (c_last == t.quote);  // (qn >= 2 then)
+  if (wave_all((n == 0) | plain | enclosed | !c.on)) {
+    const uint32_t q1 = enclosed ? 1u : 0u;
+    uint32_t npairs = 0;
+    const bool inner = c.on & enclosed & (qn > 2u);  // quote characters between the enclosing two
+    if (wave_any(inner)) {
+      if (inner) npairs = count_quote_pairs(t.qmask, c.fs + 1, c.fend - 1);
+    }
+    if (c.on) {
+      if (npairs && !t.double_quote) t.slowf[c.jj] = 1;  // errDoubleQuotesDisabled: per-row path
+      else {
+        lens[c.r] = n - 2u * q1 - npairs;
+        fstart[c.r] = (t.g0 + c.fs + q1) | (npairs ? 0x80000000u : 0u);
+        if (npairs) fstart[-1] = 1u;  // the column holds cells that are not a plain byte range
+      }
+    }
     return;
   }
   if (!c.on) return;
