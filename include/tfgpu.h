@@ -236,6 +236,12 @@ typedef enum tfgpu_rowerr {
                                     * (nginx_format.go parseEntry)                                                       */
   TFGPU_ROW_NGINX_EXTRA = 27,      /* nginx: unconsumed non-white-space behind the last token under
                                     * NginxUnexpectedFieldBehaviorError (reader_nginx_funcs.go checkUnexpectedFields)    */
+  TFGPU_ROW_PROTO_UNMARSHAL = 28,  /* protobuf parser: the event's bytes do not unmarshal (bad wire form, invalid UTF-8 in a proto3 string) */
+  TFGPU_ROW_PROTO_REQUIRED = 29,   /* protobuf parser: "required field '%s' was not populated" (column = the schema column)                 */
+  TFGPU_ROW_PROTO_FRAME_CORRUPTED = 30,  /* protoseq: "frame corrupted" — an oversized size or a sync mismatch, resynchronised at the next magic */
+  TFGPU_ROW_PROTO_FRAME_INCOMPLETE = 31, /* protoseq: "last incomplete protoseq message" — the frame is cut by the message's end               */
+  TFGPU_ROW_PROTO_FRAME_SHORT = 32,      /* protoseq: "last incomplete protoseq message: expected size len = 4, got size len = %d"            */
+  TFGPU_ROW_PROTO_WRAPPER = 33,    /* repeated: the wrapper does not unmarshal ("error creating scanner"): ONE item holds the whole value    */
   TFGPU_ROW_DBZ_FIELD = 23         /* a schema field is missing from before / after, or receiveField rejects its value
                                       (receiver.go:216-230, receiver_engine.go:148-287)                                 */
 } tfgpu_rowerr;
@@ -1408,6 +1414,53 @@ int tfgpu_raw_to_table_check_sizes(const tfgpu_message_batch *batch);
 /* the UTF-8 validator's geometry: bytes one lane takes of a long message per step, and the length from which the wave validates a message together */
 int tfgpu_rawtt_chunk_bytes(void);
 int tfgpu_rawtt_long_bytes(void);
+
+/* ---- protobuf parser ingest (pkg/parsers/registry/protobuf: ParserConfigProtoCommon / ParserConfigProtoLb → protoparser.ProtoParser) -----------
+ * The schema arrives as a serialized FileDescriptorSet (a `.desc` file); a queue message holds one event (single), a chain of protoseq frames
+ * (u32 LE size | payload | 32-byte magic) or one wrapper message whose only field is a repeated message (repeated).
+ * TimeField and TableSplitter are always nil in the reference's two configs and have no counterpart here.                                        */
+enum { TFGPU_PROTO_PKG_PROTOSEQ = 0, TFGPU_PROTO_PKG_REPEATED = 1, TFGPU_PROTO_PKG_SINGLE = 2 };
+typedef struct tfgpu_proto_col_param { const char *name; int32_t required; } tfgpu_proto_col_param;   /* protoparser.ColParams */
+typedef struct tfgpu_proto_parser_config {
+  const void *desc_file; uint64_t desc_file_len;  /* DescFile: the FileDescriptorSet's bytes                                       */
+  const char *desc_resource_name;                 /* DescResourceName: non-empty → TFGPU_ERR_UNSUPPORTED (resources are the shim's) */
+  const char *message_name;                       /* MessageName: a top-level message by its short name                            */
+  const tfgpu_proto_col_param *include_columns; int32_t n_include_columns;
+  const char *const *primary_keys; int32_t n_primary_keys;
+  int32_t package_type;                           /* TFGPU_PROTO_PKG_*                                                             */
+  int32_t null_keys_allowed, add_system_columns, skip_dedup_keys, add_synthetic_keys, not_fill_empty_fields;  /* Common: the middle three are 0 */
+} tfgpu_proto_parser_config;
+typedef struct tfgpu_proto_parser tfgpu_proto_parser;
+/* Host code, no GPU needed.  Every config error of ToProtoParserConfig / SetDescriptors / NewProtoParser is TFGPU_ERR_CONFIG with the
+ * reference's text.  A short message name that two files of the set both define is refused by name (TFGPU_ERR_UNSUPPORTED: the reference's
+ * pick depends on registry order).  _create_json takes json.Marshal of ParserConfigProtoCommon or ParserConfigProtoLb (DescFile is base64,
+ * PackageType one of "PackageTypeProtoseq" / "PackageTypeRepeated" / "PackageTypeSingleMsg").                                                   */
+int tfgpu_proto_parser_create(const tfgpu_proto_parser_config *cfg, tfgpu_proto_parser **out);
+int tfgpu_proto_parser_create_json(const char *config_json, tfgpu_proto_parser **out);
+void tfgpu_proto_parser_free(tfgpu_proto_parser *h);
+/* The result TableSchema exactly as NewProtoParser orders and flags it: keys, IncludeColumns (or every field in declaration order),
+ * `_lb_extra_<name>` for the rest under AddSystemColumns, then _partition / _offset / _idx and _lb_ctime / _lb_wtime.  enum → int32,
+ * string → utf8, bytes → string, list / map / message → any.  Free with tfgpu_schema_free.                                                    */
+int tfgpu_proto_parser_schema(const tfgpu_proto_parser *h, tfgpu_schema **out);
+/* code = TFGPU_ROW_OK: the device decodes the events; TFGPU_ROW_HOST_FALLBACK with `why` naming the construct: a COLUMN field outside the
+ * device subset (deeper nesting, a oneof inside a nested message, maps with other than string keys or with message values, groups, proto2
+ * files, repeated members inside a message) — every event then gets that code.  A field that is no column and lies outside the subset only
+ * sends the events that carry it to the host.  why / message are owned by the handle.                                                         */
+int tfgpu_proto_parser_info(const tfgpu_proto_parser *h, int32_t *code, const char **why, const char **message, int32_t *ncolumns);
+/* One failing or host-bound event: the shim builds the `_unparsed` item from it (Counter = idx, data = the span) or re-parses the span.
+ * event = the event's ordinal over the batch (failed events count), msg = its message, idx = its counter inside the message (from 1).
+ * code = TFGPU_ROW_PROTO_* / TFGPU_ROW_HOST_FALLBACK; column = the schema column of TFGPU_ROW_PROTO_REQUIRED, else -1.  [start, start + len)
+ * are the event's bytes inside batch->values: a protoseq payload (the failing forms: the bytes the reference puts into `data`, the size
+ * field included where it does), a repeated element's wire bytes (the stock code re-marshals), the whole value for TFGPU_ROW_PROTO_WRAPPER
+ * and for a repeated message the device leaves to the host as a whole (idx = 0 then: its events are not counted one by one).                    */
+typedef struct tfgpu_proto_unparsed { int64_t event; int64_t msg; uint64_t start; uint32_t len; int32_t idx; int32_t code; int32_t column; } tfgpu_proto_unparsed;
+/* ProtoParser.DoBatch.  *out = the parsed rows in event order, table = the topic with '/' and '@' replaced by '_', src_row = the event's
+ * ordinal, part_id = its message index; `_idx` = the event's counter.  unparsed[cap] / *nunparsed: the events that are not rows (when there
+ * are more than cap, *nunparsed still says how many).  event_base (HOST, [nmsg + 1], optional): a parsed row's Counter is
+ * src_row − event_base[msg] + 1.  create_time_ns (HOST or DEVICE as batch->mem, [nmsg], optional; NULL = 0) is Message.CreateTime for
+ * `_lb_ctime`: tfgpu_message_batch has no such field.  TFGPU_ERR_UNSUPPORTED by name: values reaching 4 GiB, a text column reaching 4 GiB.      */
+int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu_message_batch *batch, const int64_t *create_time_ns, tfgpu_dbatch **out,
+                             tfgpu_proto_unparsed *unparsed, int64_t cap, int64_t *nunparsed, int64_t *event_base);
 
 /* ---- profiling hooks (bench.py / rocprof cross-check) ------------------- */
 /* Per-kernel accumulated device time measured with HIP events on the library

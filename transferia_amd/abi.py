@@ -38,7 +38,8 @@ ROWERR = {0: "OK", 1: "UNSUPPORTED_KIND", 2: "COLUMN_NOT_FOUND", 3: "INT_OVERFLO
           6: "CAST", 7: "RANGE", 8: "QUOTE", 9: "DOUBLE_QUOTE", 10: "QUOTING_DISABLED", 11: "HOST_FALLBACK",
           12: "JSON_SYNTAX", 13: "PARSE_VAL", 14: "NIL_KEY", 15: "SR_SHORT", 16: "SR_MAGIC", 17: "SR_TYPE", 18: "SR_REQUIRED",
           19: "DBZ_UNPACK", 20: "DBZ_PAYLOAD", 21: "DBZ_OP", 22: "DBZ_SCHEMA", 23: "DBZ_FIELD", 24: "DROPPED", 25: "SR_PROTO",
-          26: "NGINX_FORMAT", 27: "NGINX_EXTRA"}
+          26: "NGINX_FORMAT", 27: "NGINX_EXTRA", 28: "PROTO_UNMARSHAL", 29: "PROTO_REQUIRED", 30: "PROTO_FRAME_CORRUPTED",
+          31: "PROTO_FRAME_INCOMPLETE", 32: "PROTO_FRAME_SHORT", 33: "PROTO_WRAPPER"}
 ROWERR_ID = {v: k for k, v in ROWERR.items()}
 for _k, _v in ROWERR.items():
     globals()["ROW_" + _v] = _k
@@ -162,6 +163,23 @@ class CRawToTableConfig(C.Structure):
 
 
 RTT_MAIN, RTT_DLQ = 0, 1
+
+
+class CProtoColParam(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("required", C.c_int32)]
+
+
+class CProtoParserConfig(C.Structure):
+    _fields_ = [("desc_file", C.c_void_p), ("desc_file_len", C.c_uint64), ("desc_resource_name", C.c_char_p), ("message_name", C.c_char_p),
+                ("include_columns", C.POINTER(CProtoColParam)), ("n_include_columns", C.c_int32),
+                ("primary_keys", C.POINTER(C.c_char_p)), ("n_primary_keys", C.c_int32), ("package_type", C.c_int32),
+                ("null_keys_allowed", C.c_int32), ("add_system_columns", C.c_int32), ("skip_dedup_keys", C.c_int32),
+                ("add_synthetic_keys", C.c_int32), ("not_fill_empty_fields", C.c_int32)]
+
+
+PROTO_PKG_PROTOSEQ, PROTO_PKG_REPEATED, PROTO_PKG_SINGLE = 0, 1, 2
+PROTO_PKG = {"PackageTypeProtoseq": 0, "PackageTypeRepeated": 1, "PackageTypeSingleMsg": 2}
+PROTO_UNPARSED_DTYPE = np.dtype([("event", "<i8"), ("msg", "<i8"), ("start", "<u8"), ("len", "<u4"), ("idx", "<i4"), ("code", "<i4"), ("column", "<i4")])
 
 
 def message_batch(topic: str, partition: int, msgs) -> CMessageBatch:

@@ -38,6 +38,8 @@ EXPORTS = [
     "tfgpu_tablesplit_row_tables", "tfgpu_tablesplit_batch", "tfgpu_tablesplit_free",
     "tfgpu_raw_to_table_create", "tfgpu_raw_to_table_create_json", "tfgpu_raw_to_table_free", "tfgpu_raw_to_table_schema", "tfgpu_raw_to_table_table_name",
     "tfgpu_raw_to_table_parse", "tfgpu_raw_to_table_check_sizes", "tfgpu_rawtt_chunk_bytes", "tfgpu_rawtt_long_bytes",
+    "tfgpu_proto_parser_create", "tfgpu_proto_parser_create_json", "tfgpu_proto_parser_free", "tfgpu_proto_parser_schema", "tfgpu_proto_parser_info",
+    "tfgpu_proto_parser_parse",
 ]
 
 
@@ -178,6 +180,13 @@ def load():
     L.tfgpu_raw_to_table_table_name.argtypes = [P, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]
     L.tfgpu_raw_to_table_parse.argtypes = [P, C.POINTER(abi.CMessageBatch), C.POINTER(P), C.POINTER(P), P, C.POINTER(C.c_int64)]
     L.tfgpu_raw_to_table_check_sizes.argtypes = [C.POINTER(abi.CMessageBatch)]
+    L.tfgpu_proto_parser_create.argtypes = [C.POINTER(abi.CProtoParserConfig), C.POINTER(P)]
+    L.tfgpu_proto_parser_create_json.argtypes = [C.c_char_p, C.POINTER(P)]
+    L.tfgpu_proto_parser_free.argtypes = [P]
+    L.tfgpu_proto_parser_free.restype = None
+    L.tfgpu_proto_parser_schema.argtypes = [P, C.POINTER(C.POINTER(abi.CSchema))]
+    L.tfgpu_proto_parser_info.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
+    L.tfgpu_proto_parser_parse.argtypes = [P, C.POINTER(abi.CMessageBatch), P, C.POINTER(P), P, C.c_int64, C.POINTER(C.c_int64), P]
     _lib = L
     return L
 
@@ -1335,6 +1344,90 @@ class RawToTable:
     def free(self):
         if self._h:
             load().tfgpu_raw_to_table_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ProtoParser:
+    """The protobuf parser (pkg/parsers/registry/protobuf): create / schema / info are host code and need no GPU; parse runs the device."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def create(desc_file: bytes, message_name: str, package_type="PackageTypeSingleMsg", include_columns=(), primary_keys=(), null_keys_allowed=False,
+               add_system_columns=False, skip_dedup_keys=False, add_synthetic_keys=False, not_fill_empty_fields=False, desc_resource_name="") -> "ProtoParser":
+        """ParserConfigProtoLb by its fields (ParserConfigProtoCommon: the three Lb-only flags stay False).  include_columns: [(name, required)]"""
+        c = abi.CProtoParserConfig()
+        buf = (C.c_char * max(len(desc_file), 1)).from_buffer_copy(bytes(desc_file) or b"\0")
+        c.desc_file, c.desc_file_len = C.cast(buf, C.c_void_p), len(desc_file)
+        c.desc_resource_name, c.message_name = desc_resource_name.encode(), message_name.encode()
+        inc = (abi.CProtoColParam * max(len(include_columns), 1))()
+        for i, (name, req) in enumerate(include_columns):
+            inc[i].name, inc[i].required = name.encode(), int(bool(req))
+        keys = (C.c_char_p * max(len(primary_keys), 1))(*[k.encode() for k in primary_keys])
+        c.include_columns, c.n_include_columns, c.primary_keys, c.n_primary_keys = inc, len(include_columns), keys, len(primary_keys)
+        c.package_type = abi.PROTO_PKG.get(package_type, -1) if isinstance(package_type, str) else int(package_type)
+        c.null_keys_allowed, c.add_system_columns, c.skip_dedup_keys = int(null_keys_allowed), int(add_system_columns), int(skip_dedup_keys)
+        c.add_synthetic_keys, c.not_fill_empty_fields = int(add_synthetic_keys), int(not_fill_empty_fields)
+        h = C.c_void_p()
+        _check(load().tfgpu_proto_parser_create(C.byref(c), C.byref(h)))
+        return ProtoParser(h)
+
+    @staticmethod
+    def from_config(config) -> "ProtoParser":
+        """json.Marshal of ParserConfigProtoCommon / ParserConfigProtoLb (a dict or its text; DescFile base64)"""
+        text = config if isinstance(config, (str, bytes)) else json.dumps(config)
+        h = C.c_void_p()
+        _check(load().tfgpu_proto_parser_create_json(text.encode() if isinstance(text, str) else text, C.byref(h)))
+        return ProtoParser(h)
+
+    def schema(self) -> abi.Schema:
+        out = C.POINTER(abi.CSchema)()
+        _check(load().tfgpu_proto_parser_schema(self._h, C.byref(out)))
+        try:
+            return abi.Schema.from_c(out.contents)
+        finally:
+            load().tfgpu_schema_free(out)
+
+    def info(self):
+        """(code, why, the event message's full name, number of columns): code ROW_OK, or ROW_HOST_FALLBACK with `why` naming the construct"""
+        code, why, msg, nc = C.c_int32(0), C.c_char_p(), C.c_char_p(), C.c_int32(0)
+        _check(load().tfgpu_proto_parser_info(self._h, C.byref(code), C.byref(why), C.byref(msg), C.byref(nc)))
+        return int(code.value), (why.value or b"").decode(), (msg.value or b"").decode(), int(nc.value)
+
+    def parse(self, batch: abi.CMessageBatch, create_time_ns=None, cap: Optional[int] = None, event_base: bool = True):
+        """ProtoParser.DoBatch → (DeviceBatch of the parsed rows, unparsed entries as a PROTO_UNPARSED_DTYPE array, event_base int64[nmsg + 1] or None).
+        create_time_ns lives where the batch's arrays live (batch.mem): a host array, or a device pointer as an int"""
+        init()
+        n = int(batch.nmsg)
+        ct = None
+        if isinstance(create_time_ns, int):
+            ctp = create_time_ns
+        else:
+            ct = np.ascontiguousarray(create_time_ns, dtype=np.int64) if create_time_ns is not None else None
+            assert ct is None or len(ct) == n
+            ctp = ct.ctypes.data if ct is not None and n else None
+        base = np.zeros(n + 1, np.int64) if event_base else None
+        cap = 1024 if cap is None else int(cap)
+        while True:
+            un = np.zeros(max(cap, 1), abi.PROTO_UNPARSED_DTYPE)
+            out, nu = C.c_void_p(), C.c_int64(0)
+            _check(load().tfgpu_proto_parser_parse(self._h, C.byref(batch), ctp, C.byref(out), un.ctypes.data, cap, C.byref(nu),
+                                                   base.ctypes.data if base is not None else None))
+            if int(nu.value) <= cap:
+                return DeviceBatch(out), un[: int(nu.value)].copy(), base
+            load().tfgpu_dbatch_free(out)
+            cap = int(nu.value)
+
+    def free(self):
+        if self._h:
+            load().tfgpu_proto_parser_free(self._h)
             self._h = None
 
     def __del__(self):
