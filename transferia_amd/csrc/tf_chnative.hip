@@ -24,6 +24,7 @@
 // Kernels are pure HBM streaming: one lane per value, 4/8-byte loads and stores; text columns are a length pass, one
 // segmented scan over all of them, and a copy pass.
 #include "tf_devcol.hpp"
+#include "tf_ingest.hpp"
 
 #include <cstring>
 
@@ -198,13 +199,6 @@ bool repr_fits(int repr, ChBase b) {
 
 }  // namespace
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 extern "C" int tfgpu_ch_native_block(const tfgpu_dbatch *in, const tfgpu_ch_native_column *cols, int32_t ncols, tfgpu_dbuf **out) {
   TF_API_BEGIN
   tf::dense(in);  // its rows may still be a selection (tfgpu_dbatch::pending)
@@ -237,23 +231,23 @@ extern "C" int tfgpu_ch_native_block(const tfgpu_dbatch *in, const tfgpu_ch_nati
   KernelTimer timer("ch_native_block");
   // text columns: encoded length of every cell, one segmented scan, totals read back once
   const int nstr = (int)text.size();
-  const int64_t stride = ((n + 1 + 3) / 4) * 4;
-  Buf lens, dstr;
+  const int64_t stride = TextSegments::stride(n);
+  TextSegments lens;
+  Buf dstr;
   Buf bad = dalloc(16);
   TF_HIP(hipMemsetAsync(bad->p, 0xff, 16, st));
   std::vector<StrCol> hstr((size_t)std::max(nstr, 1));
   std::vector<uint64_t> str_bytes((size_t)std::max(nstr, 1), 0);
   if (nstr) {
-    lens = dalloc_zero((size_t)nstr * (size_t)stride * 4 + 16);
+    lens = TextSegments(nstr, n);
     for (int k = 0; k < nstr; k++) hstr[(size_t)k] = StrCol{ptr<uint32_t>(text[(size_t)k]->offsets), ptr<uint8_t>(text[(size_t)k]->payload()), ptr<uint8_t>(text[(size_t)k]->validity), 0,
                                                                  text[(size_t)k]->repr == TFGPU_R_JSON ? 1 : 0};
     dstr = upload_small(hstr.data(), hstr.size() * sizeof(StrCol));
     if (n) {
-      chn_str_len<<<dim3((unsigned)((n + 255) / 256), (unsigned)nstr), 256, 0, st>>>(ptr<StrCol>(dstr), n, stride, ptr<uint32_t>(lens), ptr<unsigned long long>(bad) + 1);
-      exclusive_scan_u32_segments(ptr<uint32_t>(lens), n, nstr, stride);
-      const uint32_t *tot = segment_totals_to_host(ptr<uint32_t>(lens), n, nstr, stride);
+      chn_str_len<<<dim3((unsigned)((n + 255) / 256), (unsigned)nstr), 256, 0, st>>>(ptr<StrCol>(dstr), n, stride, lens.seg(0), ptr<unsigned long long>(bad) + 1);
+      lens.scan(false);
       sync();
-      for (int k = 0; k < nstr; k++) str_bytes[(size_t)k] = tot[k];
+      for (int k = 0; k < nstr; k++) str_bytes[(size_t)k] = lens.total(k);
     }
   }
   // layout
@@ -303,7 +297,7 @@ extern "C" int tfgpu_ch_native_block(const tfgpu_dbatch *in, const tfgpu_ch_nati
     }
     if (nstr) {
       dstr = upload_small(hstr.data(), hstr.size() * sizeof(StrCol));
-      chn_str_write<<<dim3(g, (unsigned)nstr), 256, 0, st>>>(ptr<StrCol>(dstr), n, stride, ptr<uint32_t>(lens), o);
+      chn_str_write<<<dim3(g, (unsigned)nstr), 256, 0, st>>>(ptr<StrCol>(dstr), n, stride, lens.seg(0), o);
     }
   }
   uint64_t first_bad_[2] = {0, 0};

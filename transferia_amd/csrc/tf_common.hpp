@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -67,7 +68,18 @@ struct Error : std::runtime_error {
 void set_last_error(const std::string &m);
 int fail(int code, const std::string &m);  // sets last error, returns code
 
-#define TF_HIP(expr)                                                                              \
+// the body of a C ABI entry: what it throws becomes its return code and the thread's last error
+#define TF_API_BEGIN try {
+#define TF_API_END                                                        \
+  }                                                                       \
+  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
+  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
+  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
+
+// blocks of `threads` that cover n items, at least one (a launch of zero blocks is an error)
+inline unsigned grid_for(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
+
+#define TF_HIP(expr)                                                                             \
   do {                                                                                            \
     hipError_t e__ = (expr);                                                                      \
     if (e__ != hipSuccess)                                                                        \

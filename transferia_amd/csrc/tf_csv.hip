@@ -1976,15 +1976,6 @@ static void materialize_from(const tfgpu_dbatch &b, const uint8_t *text) { mater
 
 using namespace tf;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
-static inline unsigned blocks_for(int64_t n, int t) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
-
 // ---- csv.Splitter (pkg/csv/splitter.go:37-85): entries end at the '\n's that are outside double quotes ----
 namespace tf {
 __global__ void __launch_bounds__(256) csv_split_count(const uint8_t *data, const uint32_t *row_start, int64_t nlines, uint32_t *quotes) {
@@ -2032,12 +2023,12 @@ extern "C" int tfgpu_csv_split_rows(const void *bytes, uint64_t len, int mem, tf
   res->mem = dalloc((size_t)(nl + 1) * 4 + 64);
   if (nl) {
     Buf q = dalloc((size_t)(nl + 1) * 4), qs = dalloc((size_t)(nl + 1) * 4), keep = dalloc((size_t)(nl + 1) * 4);
-    csv_split_count<<<blocks_for(nl, 256), 256, 0, st>>>(data, ptr<uint32_t>(rs), nl, ptr<uint32_t>(q));
+    csv_split_count<<<grid_for(nl, 256), 256, 0, st>>>(data, ptr<uint32_t>(rs), nl, ptr<uint32_t>(q));
     exclusive_scan_u32(ptr<uint32_t>(q), ptr<uint32_t>(qs), nl, false);
-    csv_split_keep<<<blocks_for(nl, 256), 256, 0, st>>>(ptr<uint32_t>(qs), ptr<uint32_t>(q), nl, ptr<uint32_t>(keep));
+    csv_split_keep<<<grid_for(nl, 256), 256, 0, st>>>(ptr<uint32_t>(qs), ptr<uint32_t>(q), nl, ptr<uint32_t>(keep));
     exclusive_scan_u32(ptr<uint32_t>(keep), ptr<uint32_t>(keep), nl, true);
     const uint32_t *h = d2h_u32(ptr<uint32_t>(keep) + nl);
-    csv_split_scatter<<<blocks_for(nl, 256), 256, 0, st>>>(ptr<uint32_t>(keep), ptr<uint32_t>(rs), nl, ptr<uint32_t>(res->mem));
+    csv_split_scatter<<<grid_for(nl, 256), 256, 0, st>>>(ptr<uint32_t>(keep), ptr<uint32_t>(rs), nl, ptr<uint32_t>(res->mem));
     tf::sync();
     m = *h;
   }
@@ -2156,7 +2147,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     ml_begin = dalloc((size_t)(nlines + 1) * 4); ml_end = dalloc((size_t)(nlines + 1) * 4);
     if (nlines) {
       KernelTimer t("csv_line_index");
-      csv_ml_line_fn<<<blocks_for(nlines, 256), 256, 0, st>>>(data, ptr<uint32_t>(row_start), nlines, opts->quote_char, opts->escape_char, ptr<uint8_t>(fn));
+      csv_ml_line_fn<<<grid_for(nlines, 256), 256, 0, st>>>(data, ptr<uint32_t>(row_start), nlines, opts->quote_char, opts->escape_char, ptr<uint8_t>(fn));
       csv_ml_rows<<<1, 1024, 0, st>>>(ptr<uint8_t>(fn), ptr<uint32_t>(row_start), nlines, ptr<uint32_t>(ml_begin), ptr<uint32_t>(ml_end), ptr<uint32_t>(cnt));
     }
     const uint32_t *h = d2h_u32(cnt->p);
@@ -2358,7 +2349,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   }
   if (nrows && rowpath) {
     KernelTimer t("csv_parse_rows");
-    csv_parse_rows<<<blocks_for(nrows, 256), 256, 0, st>>>(pp);
+    csv_parse_rows<<<grid_for(nrows, 256), 256, 0, st>>>(pp);
   } else if (nlines) {
     // header lines are parsed by nobody: err[] of the data rows is written by exactly one of the two kernels
     {
@@ -2367,7 +2358,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
       csv_parse_regular<<<(unsigned)(per_xcd * 8), CT_THREADS, 0, st>>>(pp);
     }
     { KernelTimer t("csv_parse_tiles_general"); csv_parse_tiles_general<<<(unsigned)std::min<int64_t>(ntiles + rtiles, 2048), CT_THREADS, 0, st>>>(pp); }
-    { KernelTimer t("csv_parse_listed"); csv_parse_listed<<<(unsigned)std::min<int64_t>(blocks_for(slow_cap, 64), 1024), 64, 0, st>>>(pp); }
+    { KernelTimer t("csv_parse_listed"); csv_parse_listed<<<(unsigned)std::min<int64_t>(grid_for(slow_cap, 64), 1024), 64, 0, st>>>(pp); }
   }
   // ---- text lengths: the tile path leaves them UNSCANNED (TextView::lens) — offsets are made when, and if, a reader asks for them
   //      (materialize() → ensure_text_offsets): a row filter in front of a sink that drops the batch or gathers the kept rows never
@@ -2381,7 +2372,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   const bool lens_state = !rowpath && src_block && !force_eager && !scan_eager;
   if (lens_state) {  // (nothing to launch)
   } else if (nrows && nstr) {
-    csv_zero_err_lens<<<blocks_for(nrows, 256), 256, 0, st>>>(ptr<uint8_t>(err), nrows, ptr<CsvCol>(bcols), ncols, ahead ? ptr<uint32_t>(tile_counts) + ngran : nullptr, skip);
+    csv_zero_err_lens<<<grid_for(nrows, 256), 256, 0, st>>>(ptr<uint8_t>(err), nrows, ptr<CsvCol>(bcols), ncols, ahead ? ptr<uint32_t>(tile_counts) + ngran : nullptr, skip);
     exclusive_scan_u32_segments(ptr<uint32_t>(lens_all), nrows, nstr, seg_stride);
   } else if (nstr) {
     TF_HIP(hipMemsetAsync(lens_all->p, 0, (size_t)nstr * (size_t)seg_stride * 4, st));
@@ -2445,7 +2436,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     if (nrows) {
       CopyParams cp{data, nrows, ptr<CopyCol>(bcc), nstr, opts->quote_char};
       KernelTimer t("csv_copy_strings");
-      csv_copy_strings<<<blocks_for(nrows, 256), 256, 0, st>>>(cp);
+      csv_copy_strings<<<grid_for(nrows, 256), 256, 0, st>>>(cp);
     }
   } else if (nstr && (!src_block || force_eager)) {
     materialize_from(*db, data);
@@ -2463,7 +2454,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
     std::vector<uint8_t> he((size_t)nrows); std::vector<int32_t> hc((size_t)nrows);
     d2h(he.data(), err->p, (size_t)nrows); d2h(hc.data(), err_col->p, (size_t)nrows * 4);
     Buf keep = dalloc((size_t)(nrows + 1) * 4);
-    csv_keep_from_err<<<blocks_for(nrows, 256), 256, 0, st>>>(ptr<uint8_t>(err), nrows, ptr<uint32_t>(keep));
+    csv_keep_from_err<<<grid_for(nrows, 256), 256, 0, st>>>(ptr<uint8_t>(err), nrows, ptr<uint32_t>(keep));
     tf::sync();
     for (int64_t r = 0; r < nrows; r++)
       if (he[(size_t)r]) { if (errs && ne < errs_cap) errs[ne] = tfgpu_row_error{r, he[(size_t)r], 0, hc[(size_t)r]}; ne++; }
@@ -2474,7 +2465,7 @@ static int csv_parse_body(const tfgpu_csv_options *opts, const tfgpu_schema *sch
   uint64_t consumed_raw = last;
   if (decoded) {  // offsets count the bytes read from the stream (reader.go:169): one past the last raw '\n'
     Buf lp = dalloc_zero(4);
-    if (raw_len) csv_last_newline<<<blocks_for((int64_t)raw_len, 256), 256, 0, st>>>(raw_data, raw_len, ptr<uint32_t>(lp));
+    if (raw_len) csv_last_newline<<<grid_for((int64_t)raw_len, 256), 256, 0, st>>>(raw_data, raw_len, ptr<uint32_t>(lp));
     const uint32_t *h = d2h_u32(lp->p);
     tf::sync();
     consumed_raw = *h;

@@ -31,6 +31,7 @@
 #include <chrono>
 #include <cstring>
 
+#include "tf_ingest.hpp"
 #include "tf_jsonscan.hpp"
 #include "tf_segcopy.hpp"
 #include "tf_wave.hpp"
@@ -991,10 +992,6 @@ __global__ void __launch_bounds__(256) dbz_pack_bits_all(const PackJob *jobs, in
   j.bits[b] = (uint8_t)v;
 }
 
-__global__ void dbz_gather_totals(const uint32_t *lens_all, int64_t seg_stride, int64_t nrows, int ntext, uint32_t *out) {
-  for (int t = threadIdx.x; t < ntext; t += blockDim.x) out[t] = lens_all[(int64_t)t * seg_stride + nrows];
-}
-
 // ---- schema-registry framed events (NewReceiver with a registry client) ---------------------------------------------------------
 // DebeziumImpl.DoOne (pkg/parsers/registry/debezium/engine/parser.go:33-57) cuts a Kafka message into events 0x00 | schema id | payload
 // exactly as the Confluent-SR parser cuts its frames (tfgpu_sr_frames); SchemaRegistry.Unpack (pkg/debezium/unpacker/schema_registry.go:
@@ -1056,33 +1053,13 @@ __global__ void __launch_bounds__(128) dbz_registry_frames(Params p, const tfgpu
   p.frames[e] = fr;
 }
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
-
-struct Staged { Buf bytes, ms; Params p{}; };
+struct Staged { Buf bytes; MessageStarts ms; Params p{}; };  // (ms.host is the upload's pageable source: it lives as long as the entry)
 static void stage(Staged &s, const void *bytes, uint64_t len, int mem, const tfgpu_messages *msgs) {
-  Context &cx = ctx();
-  if (len >= 0xFFFFFFF0ull) throw Error(TFGPU_ERR_UNSUPPORTED, "debezium: batch must be < 4 GiB (32-bit offsets)");
-  if (mem == TFGPU_MEM_HOST) {
-    s.bytes = dalloc(len + 64);
-    h2d(s.bytes->p, bytes, len);
-    TF_HIP(hipMemsetAsync((char *)s.bytes->p + len, 0, 64, cx.stream));
-    s.p.data = ptr<uint8_t>(s.bytes);
-  } else {
-    s.p.data = (const uint8_t *)bytes;
-    if (reinterpret_cast<uintptr_t>(s.p.data) & 15) throw Error(TFGPU_ERR_INVALID, "debezium: device buffer must be 16-byte aligned");
-  }
+  s.p.data = stage_input(bytes, len, mem, "debezium", s.bytes);
   const int64_t nmsg = msgs ? msgs->nmsg : 1;
   if (nmsg < 0 || (msgs && nmsg > 0 && !msgs->start)) throw Error(TFGPU_ERR_INVALID, "debezium: bad message batch");
-  std::vector<uint32_t> ms((size_t)nmsg + 1);
-  if (msgs) {
-    for (int64_t m = 0; m <= nmsg; m++) {
-      if (msgs->start[m] > len || (m && msgs->start[m] < msgs->start[m - 1])) throw Error(TFGPU_ERR_INVALID, "debezium: message offsets must be ascending and inside the buffer");
-      ms[(size_t)m] = (uint32_t)msgs->start[m];
-    }
-  } else { ms[0] = 0; ms[1] = (uint32_t)len; }
-  s.ms = dalloc(ms.size() * 4 + 16);
-  h2d(s.ms->p, ms.data(), ms.size() * 4);
-  s.p.ms = ptr<uint32_t>(s.ms); s.p.nmsg = nmsg;
+  s.ms = stage_message_starts(msgs, len, "debezium");
+  s.p.ms = ptr<uint32_t>(s.ms.dev); s.p.nmsg = nmsg;
 }
 
 }  // namespace dbz
@@ -1090,13 +1067,6 @@ static void stage(Staged &s, const void *bytes, uint64_t len, int mem, const tfg
 
 namespace tf { namespace sr { Buf last_frames_device(const tfgpu_sr_frame *host, int64_t n, const void *bytes); } }  // tf_srjson.hip
 using namespace tf;
-
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
 
 // The frames tfgpu_debezium_unpack just computed, still in HBM: the receiver (tf_dbzrecv.cpp) hands the host copy straight back to
 // tfgpu_debezium_parse, unmodified — it says so (dbz_trust_frames) and the 5 MB of frames per 2^17 messages are neither checked
@@ -1165,7 +1135,7 @@ static bool frames_stay_down(const dbz::Params &p, int64_t n, uint64_t h0, uint6
   Context &cx = ctx();
   Buf bst = dalloc(sizeof(dbz::FrameStats));
   TF_HIP(hipMemsetAsync(bst->p, 0, 16, cx.stream));
-  { KernelTimer t("dbz_frame_stats"); dbz::dbz_frame_stats<<<dbz::nblk(n, 256), 256, 0, cx.stream>>>(p.frames, n, h0, h1, p.data, reinterpret_cast<dbz::FrameStats *>(bst->p)); }
+  { KernelTimer t("dbz_frame_stats"); dbz::dbz_frame_stats<<<grid_for(n, 256), 256, 0, cx.stream>>>(p.frames, n, h0, h1, p.data, reinterpret_cast<dbz::FrameStats *>(bst->p)); }
   const dbz::FrameStats *hs = reinterpret_cast<const dbz::FrameStats *>(d2h_u32(bst->p, sizeof(dbz::FrameStats) / 4));
   tf::sync();
   if (hs->n_odd) return false;
@@ -1202,7 +1172,7 @@ static int debezium_unpack_impl(const void *bytes, uint64_t len, int mem, const 
     s.p.pframe.schema_start = known->schema_off; s.p.pframe.schema_len = known->schema_len;
     s.p.pframe.schema_hash[0] = known->schema_hash[0]; s.p.pframe.schema_hash[1] = known->schema_hash[1];
     { KernelTimer t("dbz_prefix_same"); dbz::dbz_prefix_same<<<(unsigned)((nmsg + 3) / 4), 256, 0, cx.stream>>>(s.p); }
-    { KernelTimer t("dbz_unpack"); dbz::dbz_unpack_rest<<<dbz::nblk(nmsg, 128), 128, 0, cx.stream>>>(s.p); }
+    { KernelTimer t("dbz_unpack"); dbz::dbz_unpack_rest<<<grid_for(nmsg, 128), 128, 0, cx.stream>>>(s.p); }
     hc.mark(tent ? "kernels (claimed spans)" : "kernels");
     if (frames_stay_down(s.p, nmsg, known->schema_hash[0], known->schema_hash[1], frames, bytes, fr, tent)) { hc.mark("frame stats down"); return TFGPU_OK; }
     d2h(frames, fr->p, (size_t)nmsg * sizeof(tfgpu_dbz_frame));
@@ -1219,7 +1189,7 @@ static int debezium_unpack_impl(const void *bytes, uint64_t len, int mem, const 
     tfgpu_dbz_frame f0;
     d2h(&f0, fr->p, sizeof f0);
     std::vector<uint32_t> ms01(2);
-    d2h(ms01.data(), s.ms->p, 8);
+    d2h(ms01.data(), s.ms.dev->p, 8);
     tf::sync();
     const uint64_t msg_end = ms01[1];
     // usable when the payload is the LAST member: the message is prefix + payload value + '}' (+ white space)
@@ -1229,11 +1199,11 @@ static int debezium_unpack_impl(const void *bytes, uint64_t len, int mem, const 
       Buf same = dalloc_zero((size_t)nmsg + 16);
       s.p.ref = 0; s.p.plen = (uint32_t)(f0.payload_start - ms01[0]); s.p.same = ptr<uint8_t>(same);
       { KernelTimer t("dbz_prefix_same"); dbz::dbz_prefix_same<<<(unsigned)((nmsg + 3) / 4), 256, 0, cx.stream>>>(s.p); }
-      { KernelTimer t("dbz_unpack"); dbz::dbz_unpack_rest<<<dbz::nblk(nmsg, 128), 128, 0, cx.stream>>>(s.p); }
+      { KernelTimer t("dbz_unpack"); dbz::dbz_unpack_rest<<<grid_for(nmsg, 128), 128, 0, cx.stream>>>(s.p); }
     } else {
-      KernelTimer t("dbz_unpack"); dbz::dbz_unpack<<<dbz::nblk(nmsg, 128), 128, 0, cx.stream>>>(s.p);
+      KernelTimer t("dbz_unpack"); dbz::dbz_unpack<<<grid_for(nmsg, 128), 128, 0, cx.stream>>>(s.p);
     }
-  } else if (nmsg) { KernelTimer t("dbz_unpack"); dbz::dbz_unpack<<<dbz::nblk(nmsg, 128), 128, 0, cx.stream>>>(s.p); }
+  } else if (nmsg) { KernelTimer t("dbz_unpack"); dbz::dbz_unpack<<<grid_for(nmsg, 128), 128, 0, cx.stream>>>(s.p); }
   if (nmsg) d2h(frames, fr->p, (size_t)nmsg * sizeof(tfgpu_dbz_frame));
   tf::sync();
   dbz::g_frames = dbz::FrameCache{frames, nmsg, bytes, fr, nullptr};
@@ -1273,7 +1243,7 @@ extern "C" int tfgpu_debezium_registry_frames(const void *bytes, uint64_t len, i
   if (dbz::g_tentative && !tent_off && n) { tent = dalloc_zero((size_t)n + 16); s.p.tent = ptr<uint8_t>(tent); }
   if (n) {
     if (!ev_trusted) h2d(ev->p, events, (size_t)n * sizeof(tfgpu_sr_frame));
-    { KernelTimer t("dbz_registry_frames"); dbz::dbz_registry_frames<<<dbz::nblk(n, 128), 128, 0, cx.stream>>>(s.p, reinterpret_cast<const tfgpu_sr_frame *>(ev->p)); }
+    { KernelTimer t("dbz_registry_frames"); dbz::dbz_registry_frames<<<grid_for(n, 128), 128, 0, cx.stream>>>(s.p, reinterpret_cast<const tfgpu_sr_frame *>(ev->p)); }
     if (frames_stay_down(s.p, n, dbz::g_lazy_h0, dbz::g_lazy_h1, frames, bytes, fr, tent)) return TFGPU_OK;
     d2h(frames, fr->p, (size_t)n * sizeof(tfgpu_dbz_frame));
     tf::sync();
@@ -1417,17 +1387,17 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
       if (!ff.empty()) {
         Buf bff = upload_small(ff.data(), ff.size() * 2);
         KernelTimer t("dbz_quick_floats");
-        dbz::dbz_quick_floats<<<dbz::nblk(nmsg, 128), 128, 0, st>>>(qp, ptr<uint16_t>(bff), (int)ff.size());
+        dbz::dbz_quick_floats<<<grid_for(nmsg, 128), 128, 0, st>>>(qp, ptr<uint16_t>(bff), (int)ff.size());
       }
-      { KernelTimer t("dbz_parse"); dbz::dbz_parse_listed<<<dbz::nblk(nmsg, 128), 128, 0, st>>>(p, ptr<uint32_t>(bslow) + 1, ptr<uint32_t>(bslow)); }
+      { KernelTimer t("dbz_parse"); dbz::dbz_parse_listed<<<grid_for(nmsg, 128), 128, 0, st>>>(p, ptr<uint32_t>(bslow) + 1, ptr<uint32_t>(bslow)); }
       if (const char *e = std::getenv("TFGPU_DBZ_DEBUG"); e && e[0] == '1') {  // how the messages were routed (costs a sync)
         uint32_t ns = 0;
         d2h(&ns, bslow->p, 4); tf::sync();
         std::fprintf(stderr, "tfgpu dbz quick: %lld messages, %lld tiles, %u to the walker\n", (long long)nmsg, (long long)qtiles, ns);
       }
-      dbz::dbz_first_ok<<<dbz::nblk(nmsg, 256), 256, 0, st>>>(p);
-    } else { KernelTimer t("dbz_parse"); dbz::dbz_parse<<<dbz::nblk(nmsg, 128), 128, 0, st>>>(p); }
-    dbz::dbz_table_rule<<<dbz::nblk(nmsg, 256), 256, 0, st>>>(p);
+      dbz::dbz_first_ok<<<grid_for(nmsg, 256), 256, 0, st>>>(p);
+    } else { KernelTimer t("dbz_parse"); dbz::dbz_parse<<<grid_for(nmsg, 128), 128, 0, st>>>(p); }
+    dbz::dbz_table_rule<<<grid_for(nmsg, 256), 256, 0, st>>>(p);
     dbz::dbz_table_name<<<1, 64, 0, st>>>(p, ptr<uint8_t>(tabname));
   }
   exclusive_scan_u32(p.keep, p.keep, nmsg, true);
@@ -1454,14 +1424,13 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
   p.row_msg = ptr<uint32_t>(row_msg); p.nrows = nrows;
   std::vector<dbz::OutCol> oc((size_t)std::max(nf, 1));
   std::vector<int32_t> text_cols;
-  const int64_t seg_stride = ((nrows + 1 + 3) / 4) * 4;
   int ntext = 0, nkeys = 0;
   for (int j = 0; j < nf; j++) { if (o->fields[j].op >= TFGPU_DBZ_STRING) ntext++; if (!o->fields[j].optional) nkeys++; }
   // everything the cell kernels expect zeroed, in ONE block and one memset (a 61-column table made ~200 allocations and as many
   // memset launches here: 0.36 ms of host time per batch): text lengths, the byte-per-row flags, the fixed-width values, the bitmaps
   auto a256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
   const size_t bm_bytes = a256((size_t)((nra + 7) / 8) + 8);
-  size_t zero_bytes = a256((size_t)std::max(ntext, 1) * (size_t)seg_stride * 4 + 16) + a256((size_t)std::max(nf, 1) * (size_t)nra) + a256((size_t)std::max(nkeys, 1) * (size_t)nra);
+  size_t zero_bytes = a256(TextSegments::bytes(ntext, nrows)) + a256((size_t)std::max(nf, 1) * (size_t)nra) + a256((size_t)std::max(nkeys, 1) * (size_t)nra);
   for (int j = 0; j < nf; j++) {
     const int op = o->fields[j].op;
     const size_t w = (op == TFGPU_DBZ_BOOLEAN || op == TFGPU_DBZ_INT8) ? 1 : op == TFGPU_DBZ_INT16 ? 2 : op == TFGPU_DBZ_INT32 ? 4 : (op == TFGPU_DBZ_INT64 || op == TFGPU_DBZ_FLOAT64) ? 8 : 0;
@@ -1471,7 +1440,7 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
   Buf zarena = dalloc_zero(zero_bytes);
   size_t zoff = 0;
   auto zcarve = [&](size_t bytes) { Buf b = subbuf(zarena, zoff, bytes); zoff += a256(bytes); return b; };
-  Buf lens_all = zcarve((size_t)std::max(ntext, 1) * (size_t)seg_stride * 4 + 16);
+  TextSegments text(ntext, nrows, zcarve(TextSegments::bytes(ntext, nrows)));
   Buf valid8 = zcarve((size_t)std::max(nf, 1) * (size_t)nra), oldv8 = zcarve((size_t)std::max(nkeys, 1) * (size_t)nra);
   int ti = 0, ki = 0;
   for (int j = 0; j < nf; j++) {
@@ -1495,8 +1464,8 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
       default: d.dtype = TFGPU_T_UTF8; d.repr = TFGPU_R_STRING;
     }
     if (f.op >= TFGPU_DBZ_STRING) {
-      d.offsets = subbuf(lens_all, (size_t)ti * (size_t)seg_stride * 4, (size_t)(nrows + 1) * 4);
-      c.lens = ptr<uint32_t>(d.offsets);
+      d.offsets = text.offsets(ti);
+      c.lens = text.seg(ti);
       text_cols.push_back(j);
       ti++;
     }
@@ -1513,7 +1482,7 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
   }
   Buf boc = upload_small(oc.data(), oc.size() * sizeof(dbz::OutCol));
   if (nrows) {
-    dbz::dbz_row_msgs<<<dbz::nblk(nmsg, 256), 256, 0, st>>>(p);
+    dbz::dbz_row_msgs<<<grid_for(nmsg, 256), 256, 0, st>>>(p);
     if (nf) {
       KernelTimer t("dbz_cell_values");
       std::vector<int32_t> fl[3];
@@ -1521,7 +1490,7 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
       auto launch = [&](auto kernel, const std::vector<int32_t> &l) {
         if (l.empty()) return;
         Buf bl = upload_small(l.data(), l.size() * 4);
-        kernel<<<dim3(dbz::nblk(nrows, 256), (unsigned)l.size()), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(bl), ptr<int32_t>(db->src_row), ptr<uint8_t>(db->kind), ptr<uint8_t>(old8),
+        kernel<<<dim3(grid_for(nrows, 256), (unsigned)l.size()), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(bl), ptr<int32_t>(db->src_row), ptr<uint8_t>(db->kind), ptr<uint8_t>(old8),
                                                                                 reinterpret_cast<dbz::DbzRow *>(drows->p));
       };
       launch(dbz::dbz_cell_values<dbz::DC_LIGHT>, fl[0]);
@@ -1532,22 +1501,19 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
   hc.mark("columns + cell values");
   if (nf == 0 && nrows) return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_debezium_parse: a table schema without fields");
   if (ntext) {
-    exclusive_scan_u32_segments(ptr<uint32_t>(lens_all), nrows, ntext, seg_stride);
-    Buf totals = dalloc((size_t)ntext * 4 + 16);
-    dbz::dbz_gather_totals<<<1, 64, 0, st>>>(ptr<uint32_t>(lens_all), seg_stride, nrows, ntext, ptr<uint32_t>(totals));
-    const uint32_t *tot = d2h_u32(totals->p, (size_t)ntext);   // one read-back for all the text columns' sizes, one block for their bytes
+    text.scan(false);   // one read-back for all the text columns' sizes, one block for their bytes
     static const bool words = [] { const char *e = std::getenv("TFGPU_DBZ_COPY_WORDS"); return !(e && e[0] == '0'); }();  // 0: A/B runs
     Buf spec = dalloc_zero((size_t)ntext * 4), btc0 = upload_small(text_cols.data(), text_cols.size() * 4);
-    if (nrows && words) dbz::dbz_mark_special<<<dim3(dbz::nblk(nrows, 256 * 16), (unsigned)ntext), 256, 0, st>>>(p, ptr<int32_t>(btc0), ptr<uint32_t>(spec));
+    if (nrows && words) dbz::dbz_mark_special<<<dim3(grid_for(nrows, 256 * 16), (unsigned)ntext), 256, 0, st>>>(p, ptr<int32_t>(btc0), ptr<uint32_t>(spec));
     const uint32_t *hspec = d2h_u32(spec->p, (size_t)ntext);
     tf::sync();
     size_t text_bytes = 0;
-    for (int t = 0; t < ntext; t++) text_bytes += a256((size_t)tot[t] + 8);
+    for (int t = 0; t < ntext; t++) text_bytes += a256((size_t)text.total(t) + 8);
     Buf tarena = dalloc(std::max<size_t>(text_bytes, 256));
     size_t toff = 0;
     for (int t = 0; t < ntext; t++) {
       DColumn &d = db->cols[(size_t)text_cols[(size_t)t]];
-      d.data_len = tot[t];
+      d.data_len = text.total(t);
       d.data = subbuf(tarena, toff, (size_t)d.data_len + 8);
       toff += a256((size_t)d.data_len + 8);
       oc[(size_t)text_cols[(size_t)t]].data = ptr<uint8_t>(d.data);
@@ -1557,13 +1523,13 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
     auto launch_text = [&](const std::vector<int32_t> &colsl, int plain_done) {  // the listed text columns, by receiver class
       std::vector<int32_t> lt, hv;
       for (int32_t j : colsl) (dbz::dbz_field_class(o->fields[j].op) == dbz::DC_RENDER ? hv : lt).push_back(j);
-      if (!lt.empty()) { Buf b = upload_small(lt.data(), lt.size() * 4); dbz::dbz_cell_text<false><<<dim3(dbz::nblk(nrows, 256), (unsigned)lt.size()), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(b), (int32_t)lt.size(), plain_done); }
-      if (!hv.empty()) { Buf b = upload_small(hv.data(), hv.size() * 4); dbz::dbz_cell_text<true><<<dim3(dbz::nblk(nrows, 256), (unsigned)hv.size()), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(b), (int32_t)hv.size(), plain_done); }
+      if (!lt.empty()) { Buf b = upload_small(lt.data(), lt.size() * 4); dbz::dbz_cell_text<false><<<dim3(grid_for(nrows, 256), (unsigned)lt.size()), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(b), (int32_t)lt.size(), plain_done); }
+      if (!hv.empty()) { Buf b = upload_small(hv.data(), hv.size() * 4); dbz::dbz_cell_text<true><<<dim3(grid_for(nrows, 256), (unsigned)hv.size()), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(b), (int32_t)hv.size(), plain_done); }
     };
     if (nrows) {
       KernelTimer t("dbz_cell_text");
       if (words) {
-        dbz::dbz_copy_words<<<dim3(dbz::nblk(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(btc));
+        dbz::dbz_copy_words<<<dim3(grid_for(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<dbz::OutCol>(boc), ptr<int32_t>(btc));
         std::vector<int32_t> sp;
         for (int t2 = 0; t2 < ntext; t2++) if (hspec[t2]) sp.push_back(text_cols[(size_t)t2]);
         launch_text(sp, 1);
@@ -1571,7 +1537,7 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
     }
   }
   // bitmaps: ColumnValues validity per column; OldKeys = the key columns' buffers under their own validity
-  const unsigned gb = dbz::nblk((nrows + 7) / 8, 256);
+  const unsigned gb = grid_for((nrows + 7) / 8, 256);
   std::vector<dbz::PackJob> jobs;  // one launch for all of them (a 61-column table made ~70 launches here)
   for (int j = 0; j < nf; j++) jobs.push_back(dbz::PackJob{oc[(size_t)j].valid8, oc[(size_t)j].validity});
   for (int j = 0; j < nf; j++) {
@@ -1589,7 +1555,7 @@ extern "C" int tfgpu_debezium_parse(const tfgpu_dbz_options *o, const void *byte
   if (any_toast && nrows && nf) {  // `__debezium_unavailable_value`: the columns those rows do not list (rare: its own launch and read-back)
     abs8 = dalloc((size_t)nf * (size_t)nra);
     Buf colflag = dalloc_zero((size_t)nf * 4);
-    dbz::dbz_absent_cells<<<dim3(dbz::nblk(nrows, 256), (unsigned)nf), 256, 0, st>>>(p, nra, ptr<uint8_t>(abs8), ptr<uint32_t>(colflag));
+    dbz::dbz_absent_cells<<<dim3(grid_for(nrows, 256), (unsigned)nf), 256, 0, st>>>(p, nra, ptr<uint8_t>(abs8), ptr<uint32_t>(colflag));
     const uint32_t *hcf = d2h_u32(colflag->p, (size_t)nf);
     tf::sync();
     for (int j = 0; j < nf; j++) if (hcf[j]) {

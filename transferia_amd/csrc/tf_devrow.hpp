@@ -7,11 +7,6 @@
 #include "tf_devfloat.hpp"
 
 namespace tf {
-static inline unsigned grid_for(int64_t n, int threads) {
-  int64_t b = (n + threads - 1) / threads;
-  return (unsigned)std::max<int64_t>(1, b);
-}
-
 // ============================================================================
 // SerializeToString on device (to_string.go:145-178).  Formats value r of
 // column c into `buf` (>= 64 bytes) unless the value is var-width text, in

@@ -85,7 +85,6 @@ void nccl_check(int rc, const char *what) {
 }
 #define TF_NCCL(expr) nccl_check((expr), #expr)
 
-inline unsigned grid_for(int64_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
 // ---- small device helpers ----------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) xc_lengths(const uint32_t *off, int64_t n, uint32_t *len) {
@@ -411,13 +410,6 @@ std::unique_ptr<tfgpu_dbatch> exchange(tfgpu_comm &cm, const tfgpu_dbatch &in, c
 }
 
 }  // namespace
-
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
 
 extern "C" {
 

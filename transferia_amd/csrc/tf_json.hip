@@ -32,6 +32,7 @@
 
 #include "tf_common.hpp"
 #include "tf_rows.hpp"
+#include "tf_ingest.hpp"
 #include "tf_devfmt.hpp"
 #include "tf_devfloat.hpp"
 #include "tf_devparse.hpp"
@@ -1919,18 +1920,9 @@ const double *pow10_table() {
   return ptr<double>(cx.pow10tab);
 }
 
-static inline unsigned jblocks(int64_t n, int t) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
-
 }  // namespace tf
 
 using namespace tf;
-
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
 
 namespace {
 struct AuxCol { std::string name; int dtype; uint32_t flags; };
@@ -2111,29 +2103,14 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
 
   // ---- input in HBM ----
   Buf staged;
-  const uint8_t *data;
-  if (mem == TFGPU_MEM_HOST) {
-    staged = dalloc(len + 64);
-    h2d(staged->p, bytes, len);
-    TF_HIP(hipMemsetAsync((char *)staged->p + len, 0, 64, st));
-    data = ptr<uint8_t>(staged);
-  } else {
-    data = (const uint8_t *)bytes;
-    if (reinterpret_cast<uintptr_t>(data) & 15) return tf::fail(TFGPU_ERR_INVALID, "json: device buffer must be 16-byte aligned");
-  }
+  const uint8_t *data = stage_input(bytes, len, mem, "json", staged);
   // ---- messages ----
-  const uint32_t nmsg = msgs ? (uint32_t)msgs->nmsg : 1u;
-  std::vector<uint32_t> ms((size_t)nmsg + 1);
-  if (msgs) {
-    if (msgs->nmsg < 1 || !msgs->start) return tf::fail(TFGPU_ERR_INVALID, "json: empty message batch");
-    for (uint32_t m = 0; m <= nmsg; m++) {
-      if (msgs->start[m] > len || (m && msgs->start[m] < msgs->start[m - 1])) return tf::fail(TFGPU_ERR_INVALID, "json: message offsets must be ascending and inside the buffer");
-      ms[m] = (uint32_t)msgs->start[m];
-    }
-    if (ms[0] != 0 || ms[nmsg] != len) return tf::fail(TFGPU_ERR_INVALID, "json: messages must cover the buffer");
-  } else { ms[0] = 0; ms[1] = (uint32_t)len; }
-  Buf bms = dalloc(ms.size() * 4), bmoff, bmwt;
-  h2d(bms->p, ms.data(), ms.size() * 4);
+  if (msgs && (msgs->nmsg < 1 || !msgs->start)) return tf::fail(TFGPU_ERR_INVALID, "json: empty message batch");
+  const MessageStarts ms = stage_message_starts(msgs, len, "json");
+  const uint32_t nmsg = (uint32_t)ms.nmsg();
+  if (ms.host[0] != 0 || ms.host[nmsg] != len) return tf::fail(TFGPU_ERR_INVALID, "json: messages must cover the buffer");
+  const Buf &bms = ms.dev;
+  Buf bmoff, bmwt;
   if (msgs && msgs->offset) { bmoff = dalloc((size_t)nmsg * 8); h2d(bmoff->p, msgs->offset, (size_t)nmsg * 8); }
   if (msgs && msgs->write_time_ns) { bmwt = dalloc((size_t)nmsg * 8); h2d(bmwt->p, msgs->write_time_ns, (size_t)nmsg * 8); }
 
@@ -2145,8 +2122,8 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
   Buf seg_start = dalloc((size_t)nseg * 4), seg_len = dalloc((size_t)nseg * 4), seg_ord = dalloc((size_t)(nseg + 1) * 4);
   {
     KernelTimer t("json_line_bounds");
-    json_merge_bounds<<<jblocks(nseg, 256), 256, 0, st>>>(ptr<uint32_t>(nls) + 1, nnl, ptr<uint32_t>(bms), nmsg, (uint32_t)len, ptr<uint32_t>(bounds), ptr<uint32_t>(rank_ms));
-    json_segments<<<jblocks(nseg, 256), 256, 0, st>>>(data, ptr<uint32_t>(bounds), nseg, ptr<uint32_t>(seg_start), ptr<uint32_t>(seg_len), ptr<uint32_t>(seg_ord));
+    json_merge_bounds<<<grid_for(nseg, 256), 256, 0, st>>>(ptr<uint32_t>(nls) + 1, nnl, ptr<uint32_t>(bms), nmsg, (uint32_t)len, ptr<uint32_t>(bounds), ptr<uint32_t>(rank_ms));
+    json_segments<<<grid_for(nseg, 256), 256, 0, st>>>(data, ptr<uint32_t>(bounds), nseg, ptr<uint32_t>(seg_start), ptr<uint32_t>(seg_len), ptr<uint32_t>(seg_ord));
   }
   exclusive_scan_u32(ptr<uint32_t>(seg_ord), ptr<uint32_t>(seg_ord), nseg, true);
   const uint32_t *hn = d2h_u32(ptr<uint32_t>(seg_ord) + nseg);
@@ -2265,14 +2242,14 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
       used_per_tile = qper;
       Buf bmap = dalloc(sizeof(JqMap));
       { KernelTimer t("json_quick_map"); json_quick_map<<<1, JQ_THREADS, 0, st>>>(pp, ptr<JqMap>(bmap)); }
-      { KernelTimer t("json_parse_quick"); json_parse_quick<<<jblocks(nseg, qper), JQ_THREADS, 0, st>>>(pp, ptr<JqMap>(bmap), qper, nalloc, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1, jt_ablate); }
+      { KernelTimer t("json_parse_quick"); json_parse_quick<<<grid_for(nseg, qper), JQ_THREADS, 0, st>>>(pp, ptr<JqMap>(bmap), qper, nalloc, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1, jt_ablate); }
     } else {
     // persistent workgroups (two per CU fit its LDS): each walks every (2 * CUs)-th tile and keeps its member map
-    const unsigned ntile = jblocks(nseg, per_tile), nblk = (unsigned)std::min<int64_t>((int64_t)ntile, (int64_t)cx.num_cus * 2);
-    { KernelTimer t("json_parse_tiles"); json_parse_tiles<<<nblk, JT_THREADS, 0, st>>>(pp, per_tile, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
+    const unsigned ntile = grid_for(nseg, per_tile), ngrid = (unsigned)std::min<int64_t>((int64_t)ntile, (int64_t)cx.num_cus * 2);
+    { KernelTimer t("json_parse_tiles"); json_parse_tiles<<<ngrid, JT_THREADS, 0, st>>>(pp, per_tile, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
     }
-    { KernelTimer t("json_parse_listed"); json_parse_listed_lean<<<jblocks(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1, ptr<uint32_t>(heavy), ptr<uint32_t>(heavy) + 1);
-      json_parse_listed<<<jblocks(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(heavy), ptr<uint32_t>(heavy) + 1); }
+    { KernelTimer t("json_parse_listed"); json_parse_listed_lean<<<grid_for(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1, ptr<uint32_t>(heavy), ptr<uint32_t>(heavy) + 1);
+      json_parse_listed<<<grid_for(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(heavy), ptr<uint32_t>(heavy) + 1); }
     static const bool dbg = [] { const char *e = std::getenv("TFGPU_JSON_TILE_DEBUG"); return e && e[0] == '1'; }();
     if (dbg) {  // how many lines the tile path handed over (diagnostics only: costs a synchronisation)
       const uint32_t *a = d2h_u32(slow->p), *b = d2h_u32(heavy->p);
@@ -2283,15 +2260,15 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
   else if (nlines && (!wavepath || tskv || any_nested)) {
     Buf slow = dalloc((size_t)(nseg + 1) * 4);  // lines that need the map emitter: re-parsed by the kernel that carries it
     TF_HIP(hipMemsetAsync(slow->p, 0, 4, st));
-    { KernelTimer t("json_parse_lines"); json_parse_lines<<<jblocks(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
-    if (!tskv || any_nested) { KernelTimer t("json_parse_listed"); json_parse_listed<<<jblocks(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
+    { KernelTimer t("json_parse_lines"); json_parse_lines<<<grid_for(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
+    if (!tskv || any_nested) { KernelTimer t("json_parse_listed"); json_parse_listed<<<grid_for(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
   }
   else if (nlines) {
     Buf slow = dalloc((size_t)(nseg + 1) * 4);
     TF_HIP(hipMemsetAsync(slow->p, 0, 4, st));
-    const unsigned nblk = (unsigned)std::min<int64_t>((nseg + JF_WAVES - 1) / JF_WAVES, (int64_t)cx.num_cus * 8);
-    { KernelTimer t("json_parse_waves"); json_parse_waves<<<nblk, 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
-    { KernelTimer t("json_parse_listed"); json_parse_listed<<<jblocks(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
+    const unsigned ngrid = (unsigned)std::min<int64_t>((nseg + JF_WAVES - 1) / JF_WAVES, (int64_t)cx.num_cus * 8);
+    { KernelTimer t("json_parse_waves"); json_parse_waves<<<ngrid, 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
+    { KernelTimer t("json_parse_listed"); json_parse_listed<<<grid_for(nseg, 256), 256, 0, st>>>(pp, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
   }
 
   // ---- aux columns + row rules ----
@@ -2317,7 +2294,7 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
       if ((uint64_t)text.size() * (uint64_t)nalloc >= 0xFFFFFFF0ull) return tf::fail(TFGPU_ERR_UNSUPPORTED, "json: `_partition` column exceeds 4 GiB");
       d.offsets = dalloc((size_t)(nalloc + 1) * 4); d.data = dalloc(text.size() * (size_t)nalloc + 8); d.data_len = text.size() * (uint64_t)nlines;
       Buf bt = upload_small(text.data(), text.size());
-      json_const_text<<<jblocks(nlines + 1, 256), 256, 0, st>>>(ptr<uint8_t>(bt), (uint32_t)text.size(), nlines, ptr<uint32_t>(d.offsets), ptr<uint8_t>(d.data));
+      json_const_text<<<grid_for(nlines + 1, 256), 256, 0, st>>>(ptr<uint8_t>(bt), (uint32_t)text.size(), nlines, ptr<uint32_t>(d.offsets), ptr<uint8_t>(d.data));
     } else if (a.dtype == TFGPU_T_TIMESTAMP) {
       d.repr = TFGPU_R_TIME; d.values = dalloc((size_t)nalloc * 8); d.nanos = dalloc((size_t)nalloc * 4);
       fp.ts_sec = ptr<int64_t>(d.values); fp.ts_nanos = ptr<int32_t>(d.nanos);
@@ -2327,9 +2304,9 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
   }
   if (nlines) {
     KernelTimer t("json_finish");
-    json_finish<<<jblocks(nlines, 256), 256, 0, st>>>(fp);
+    json_finish<<<grid_for(nlines, 256), 256, 0, st>>>(fp);
     Buf bvp = upload_small(valid_ptrs.data(), valid_ptrs.size() * sizeof(uint8_t *));
-    if (nraw) json_validity<<<dim3(jblocks((nlines + 7) / 8, 256), (unsigned)nraw), 256, 0, st>>>(ptr<JCol>(bcols), nlines, (uint8_t *const *)bvp->p, ptr<uint32_t>(keep), ptr<uint32_t>(has_nil));
+    if (nraw) json_validity<<<dim3(grid_for((nlines + 7) / 8, 256), (unsigned)nraw), 256, 0, st>>>(ptr<JCol>(bcols), nlines, (uint8_t *const *)bvp->p, ptr<uint32_t>(keep), ptr<uint32_t>(has_nil));
   }
   if (nstr) exclusive_scan_u32_segments(ptr<uint32_t>(lens_all), nlines, nstr, seg_stride);
   Buf spec = dalloc_zero((size_t)std::max(nstr, 1) * 4);
@@ -2337,7 +2314,7 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
     std::vector<const uint32_t *> metas((size_t)nstr);
     for (int sg = 0; sg < nstr; sg++) metas[(size_t)sg] = sg == rest_seg ? pp.rest_meta : cols[(size_t)str_col_index[(size_t)sg]].meta;
     Buf bm = upload_small(metas.data(), metas.size() * sizeof(uint32_t *));
-    json_mark_special<<<dim3(jblocks(nlines, 256 * 16), (unsigned)nstr), 256, 0, st>>>(ptr<uint32_t>(lens_all), seg_stride, (const uint32_t *const *)bm->p, nlines, ptr<uint32_t>(spec));
+    json_mark_special<<<dim3(grid_for(nlines, 256 * 16), (unsigned)nstr), 256, 0, st>>>(ptr<uint32_t>(lens_all), seg_stride, (const uint32_t *const *)bm->p, nlines, ptr<uint32_t>(spec));
   }
   Buf summary = dalloc((size_t)(2 * nstr + nraw + 1) * 4);
   json_collect<<<1, 64, 0, st>>>(ptr<uint32_t>(nerr), ptr<uint32_t>(lens_all), seg_stride, nlines, nstr, ptr<uint32_t>(has_nil), nraw, ptr<uint32_t>(spec), ptr<uint32_t>(summary));
@@ -2361,7 +2338,7 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
     Buf bcc = upload_small(cc.data(), cc.size() * sizeof(JCopyCol));
     KernelTimer t("json_copy_cells");
     static const bool words = [] { const char *e = std::getenv("TFGPU_JSON_COPY_WORDS"); return !(e && e[0] == '0'); }();  // 0: A/B runs
-    if (words) json_copy_words<<<dim3(jblocks(nlines, 256), (unsigned)nstr), 256, 0, st>>>(data, ptr<JCopyCol>(bcc), nlines);
+    if (words) json_copy_words<<<dim3(grid_for(nlines, 256), (unsigned)nstr), 256, 0, st>>>(data, ptr<JCopyCol>(bcc), nlines);
     // the walkers only where json_mark_special saw their cells (every column without TFGPU_JSON_COPY_WORDS: the plain cells are theirs then)
     std::vector<JCopyCol> light, heavy;
     for (int sg = 0; sg < nstr; sg++) {
@@ -2369,8 +2346,8 @@ extern "C" int tfgpu_json_parse(const tfgpu_json_options *opts, const tfgpu_sche
       if ((f & 1u) || !words) light.push_back(cc[(size_t)sg]);
       if (f & 2u) heavy.push_back(cc[(size_t)sg]);
     }
-    if (!light.empty()) { Buf bl = upload_small(light.data(), light.size() * sizeof(JCopyCol)); json_copy_cells<false><<<dim3(jblocks(nlines, 256), (unsigned)light.size()), 256, 0, st>>>(pp, ptr<JCopyCol>(bl), nlines, words ? 1 : 0); }
-    if (!heavy.empty()) { Buf bh = upload_small(heavy.data(), heavy.size() * sizeof(JCopyCol)); json_copy_cells<true><<<dim3(jblocks(nlines, 256), (unsigned)heavy.size()), 256, 0, st>>>(pp, ptr<JCopyCol>(bh), nlines, words ? 1 : 0); }
+    if (!light.empty()) { Buf bl = upload_small(light.data(), light.size() * sizeof(JCopyCol)); json_copy_cells<false><<<dim3(grid_for(nlines, 256), (unsigned)light.size()), 256, 0, st>>>(pp, ptr<JCopyCol>(bl), nlines, words ? 1 : 0); }
+    if (!heavy.empty()) { Buf bh = upload_small(heavy.data(), heavy.size() * sizeof(JCopyCol)); json_copy_cells<true><<<dim3(grid_for(nlines, 256), (unsigned)heavy.size()), 256, 0, st>>>(pp, ptr<JCopyCol>(bh), nlines, words ? 1 : 0); }
   }
 
   // ---- dropped lines: `_unparsed` rows / host fallback are reported, skipped lines vanish ----

@@ -18,13 +18,6 @@
 
 using namespace tf;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 // ---- the compiled format (host) ---------------------------------------------------------------------------------------------
 struct NginxToken { bool is_variable; std::string value; };
 struct tfgpu_nginx_format {

@@ -1370,13 +1370,6 @@ __global__ void __launch_bounds__(256) pq_file_name(const uint8_t *name, uint32_
 using namespace tf;
 using namespace tf::pq;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 struct NeedArena {};  // thrown by the walk when a page must be rewritten on the host (DELTA_BYTE_ARRAY) and the object was to be uploaded as it is
 
 // An uncompressed object goes up in pieces on the lane's copy stream, an event behind each: the page kernels of a piece are queued behind

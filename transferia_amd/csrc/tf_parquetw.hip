@@ -183,13 +183,6 @@ __global__ void __launch_bounds__(256) pqw_text_copy(const uint32_t *offsets, co
 using namespace tf;
 using namespace tf::pqw;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 extern "C" int tfgpu_parquet_write(const tfgpu_dbatch *b, const tfgpu_schema *schema, const char *codec_name, int64_t row_group_max_rows, uint64_t row_group_max_bytes, void **bytes, uint64_t *len) {
   TF_API_BEGIN
   tf::dense(b);  // its rows may still be a selection (tfgpu_dbatch::pending)

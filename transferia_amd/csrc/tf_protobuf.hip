@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "tf_common.hpp"
-#include "tf_rows.hpp"
+#include "tf_ingest.hpp"
 #include "tf_devfloat.hpp"
 #include "tf_devparse.hpp"
 #include "tf_emit.hpp"
@@ -217,26 +217,10 @@ template <bool WIDE> __global__ void __launch_bounds__(256) pb_text_any(Params p
   s.flush();
 }
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
-
 }  // namespace pbd
 }  // namespace tf
 
-// 32-bit offsets hold less than 4 GiB per column.  TFGPU_TEST_TEXT_LIMIT (tests only) lowers the bound so that the refusal can be
-// exercised without a 4 GiB batch.
-static bool text_total_exceeds(uint64_t bytes) {
-  static const uint64_t limit = [] { const char *e = std::getenv("TFGPU_TEST_TEXT_LIMIT"); return e && *e ? (uint64_t)std::strtoull(e, nullptr, 10) : 0xFFFFFFF0ull; }();
-  return bytes >= limit;
-}
-
 using namespace tf;
-
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
 
 extern "C" int tfgpu_pb_schema_info(const tfgpu_pb_schema *s, int32_t *code, const tfgpu_pb_field **fields, int32_t *nfields, const char **table_ns, const char **table_name, const char **record, const char **why);
 
@@ -248,33 +232,16 @@ extern "C" int tfgpu_sr_proto_parse(const tfgpu_pb_schema *sch, uint32_t schema_
   const tfgpu_pb_field *fl = nullptr;
   const char *ns = "", *table = "";
   tfgpu_pb_schema_info(sch, &code, &fl, &nf, &ns, &table, nullptr, nullptr);
-  if (len >= 0xFFFFFFF0ull) return tf::fail(TFGPU_ERR_UNSUPPORTED, "confluent SR protobuf: batch must be < 4 GiB (32-bit offsets)");
   if (nf > 4096) return tf::fail(TFGPU_ERR_UNSUPPORTED, "confluent SR protobuf: more than 4096 fields");
   Context &cx = ctx();
   std::lock_guard<std::mutex> lk(cx.mu);
   hipStream_t st = cx.stream;
   pbd::Params p{};
   Buf staged;
-  if (mem == TFGPU_MEM_HOST) {
-    staged = dalloc(len + 64);
-    h2d(staged->p, bytes, len);
-    TF_HIP(hipMemsetAsync((char *)staged->p + len, 0, 64, st));
-    p.data = ptr<uint8_t>(staged);
-  } else {
-    p.data = (const uint8_t *)bytes;
-    if (reinterpret_cast<uintptr_t>(p.data) & 15) return tf::fail(TFGPU_ERR_INVALID, "confluent SR protobuf: device buffer must be 16-byte aligned");
-  }
+  p.data = stage_input(bytes, len, mem, "confluent SR protobuf", staged);
   const int64_t nmsg = msgs ? msgs->nmsg : 1, nma = std::max<int64_t>(nmsg, 1);
   if (nmsg < 0 || (msgs && nmsg > 0 && !msgs->start)) return tf::fail(TFGPU_ERR_INVALID, "confluent SR protobuf: bad message batch");
-  std::vector<uint32_t> ms((size_t)nmsg + 1);
-  if (msgs) {
-    for (int64_t m = 0; m <= nmsg; m++) {
-      if (msgs->start[m] > len || (m && msgs->start[m] < msgs->start[m - 1])) return tf::fail(TFGPU_ERR_INVALID, "confluent SR protobuf: message offsets must be ascending and inside the buffer");
-      ms[(size_t)m] = (uint32_t)msgs->start[m];
-    }
-  } else { ms[0] = 0; ms[1] = (uint32_t)len; }
-  Buf bms = dalloc(ms.size() * 4 + 16);
-  h2d(bms->p, ms.data(), ms.size() * 4);
+  const MessageStarts ms = stage_message_starts(msgs, len, "confluent SR protobuf");
   // the descriptor tables
   std::vector<pbd::DField> fields((size_t)std::max(nf, 1));
   std::vector<pbd::DMember> members(1);
@@ -298,11 +265,11 @@ extern "C" int tfgpu_sr_proto_parse(const tfgpu_pb_schema *sch, uint32_t schema_
   Buf bfields = upload_small(fields.data(), fields.size() * sizeof(pbd::DField)), bmembers = upload_small(members.data(), members.size() * sizeof(pbd::DMember)), bnames = upload_small(names.data(), names.size());
   Buf rec = dalloc((size_t)std::max(nf, 1) * (size_t)nma * 8 + 16), present = dalloc((size_t)std::max(nf, 1) * (size_t)nma + 16);
   Buf status = dalloc_zero((size_t)nma + 16), keep = dalloc_zero((size_t)(nma + 1) * 4 + 16), nerr = dalloc_zero(16);
-  p.ms = ptr<uint32_t>(bms); p.nmsg = nmsg; p.schema_id = schema_id; p.schema_code = code; p.report_frame_errors = report_frame_errors;
+  p.ms = ptr<uint32_t>(ms.dev); p.nmsg = nmsg; p.schema_id = schema_id; p.schema_code = code; p.report_frame_errors = report_frame_errors;
   p.fields = ptr<pbd::DField>(bfields); p.nfields = code == TFGPU_ROW_OK ? nf : 0; p.members = ptr<pbd::DMember>(bmembers); p.names = ptr<uint8_t>(bnames);
   p.lut = ptr<int16_t>(blut); p.lutn = (int32_t)lut.size();
   p.rec = ptr<uint64_t>(rec); p.present = ptr<uint8_t>(present); p.status = ptr<uint8_t>(status); p.keep = ptr<uint32_t>(keep); p.nerr = ptr<uint32_t>(nerr);
-  if (nmsg) { KernelTimer t("pb_decode"); pbd::pb_decode<<<pbd::nblk(nmsg, 128), 128, 0, st>>>(p); }
+  if (nmsg) { KernelTimer t("pb_decode"); pbd::pb_decode<<<grid_for(nmsg, 128), 128, 0, st>>>(p); }
   exclusive_scan_u32(p.keep, p.keep, nmsg, true);
   const uint32_t *hrows = d2h_u32(p.keep + nmsg), *hnerr = d2h_u32(p.nerr);
   tf::sync();
@@ -318,14 +285,11 @@ extern "C" int tfgpu_sr_proto_parse(const tfgpu_pb_schema *sch, uint32_t schema_
   p.row_msg = ptr<uint32_t>(row_msg); p.nrows = nrows;
   std::vector<pbd::OutCol> oc((size_t)std::max(nf, 1));
   std::vector<int32_t> text_cols;
-  const int64_t seg_stride = ((nrows + 1 + 3) / 4) * 4;
   int ntext = 0;
   bool has_msg = false;
   for (int j = 0; j < nf; j++) { const int t = fl[j].ptype; if (fl[j].repeated || t == TFGPU_PB_STRING || t == TFGPU_PB_BYTES || t == TFGPU_PB_MESSAGE) ntext++; if (fl[j].repeated || t == TFGPU_PB_MESSAGE) has_msg = true; }
-  Buf lens_all = dalloc_zero((size_t)std::max(ntext, 1) * (size_t)seg_stride * 4 + 16);
-  // the columns' validity bitmaps as views of one block cleared by one fill (a fill per column was two dispatches each: 0.6 ms of a 60-column batch)
-  const size_t vbytes = ((size_t)((nra + 63) / 64) * 8 + 8 + 63) & ~(size_t)63;
-  Buf valid_all = dalloc_zero((size_t)std::max(nf, 1) * vbytes);
+  TextSegments text(ntext, nrows);
+  const ValidityBlock valid(nf, nrows);  // (a fill per column was 0.6 ms of a 60-column batch)
   int ti = 0;
   for (int j = 0; j < nf; j++) {
     DColumn d;
@@ -350,12 +314,12 @@ extern "C" int tfgpu_sr_proto_parse(const tfgpu_pb_schema *sch, uint32_t schema_
       default: return tf::fail(TFGPU_ERR_INVALID, "tfgpu_sr_proto_parse: bad field type");
     }
     if (!d.values) {
-      d.offsets = subbuf(lens_all, (size_t)ti * (size_t)seg_stride * 4, (size_t)(nrows + 1) * 4);
-      c.lens = ptr<uint32_t>(d.offsets);
+      d.offsets = text.offsets(ti);
+      c.lens = text.seg(ti);
       text_cols.push_back(j);
       ti++;
     }
-    d.validity = subbuf(valid_all, (size_t)j * vbytes, (size_t)((nra + 63) / 64) * 8 + 8);
+    d.validity = valid.col(j);
     c.validity = ptr<uint8_t>(d.validity);
     db->schema.push_back({d.name, d.dtype});
     db->cols.push_back(std::move(d));
@@ -365,30 +329,26 @@ extern "C" int tfgpu_sr_proto_parse(const tfgpu_pb_schema *sch, uint32_t schema_
   for (int j = 0; j < nf; j++) (wide(j) ? wide_cols : (fl[j].repeated || fl[j].ptype == TFGPU_PB_MESSAGE) ? any_cols : light_cols).push_back(j);
   Buf boc = upload_small(oc.data(), oc.size() * sizeof(pbd::OutCol));
   if (nrows) {
-    pbd::pb_row_msgs<<<pbd::nblk(nmsg, 256), 256, 0, st>>>(p);
+    pbd::pb_row_msgs<<<grid_for(nmsg, 256), 256, 0, st>>>(p);
     KernelTimer t("pb_cells");
     const int32_t none = 0;
     Buf bl = light_cols.empty() ? upload_small(&none, 4) : upload_small(light_cols.data(), light_cols.size() * 4), ba = any_cols.empty() ? upload_small(&none, 4) : upload_small(any_cols.data(), any_cols.size() * 4);
-    if (!light_cols.empty()) pbd::pb_cells<false><<<dim3(pbd::nblk(nrows, 256), (unsigned)light_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bl), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id), ptr<uint32_t>(host_rows));
-    else pbd::pb_src_rows<<<pbd::nblk(nrows, 256), 256, 0, st>>>(p, ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id));
-    if (!any_cols.empty()) pbd::pb_cells<true><<<dim3(pbd::nblk(nrows, 256), (unsigned)any_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(ba), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id), ptr<uint32_t>(host_rows));
-    if (!wide_cols.empty()) { Buf bw = upload_small(wide_cols.data(), wide_cols.size() * 4); pbd::pb_cells<true, true><<<dim3(pbd::nblk(nrows, 256), (unsigned)wide_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bw), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id), ptr<uint32_t>(host_rows)); }
+    if (!light_cols.empty()) pbd::pb_cells<false><<<dim3(grid_for(nrows, 256), (unsigned)light_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bl), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id), ptr<uint32_t>(host_rows));
+    else pbd::pb_src_rows<<<grid_for(nrows, 256), 256, 0, st>>>(p, ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id));
+    if (!any_cols.empty()) pbd::pb_cells<true><<<dim3(grid_for(nrows, 256), (unsigned)any_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(ba), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id), ptr<uint32_t>(host_rows));
+    if (!wide_cols.empty()) { Buf bw = upload_small(wide_cols.data(), wide_cols.size() * 4); pbd::pb_cells<true, true><<<dim3(grid_for(nrows, 256), (unsigned)wide_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bw), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id), ptr<uint32_t>(host_rows)); }
   }
   if (ntext) {
     // The `any` marshalling expands its input (absent members as "name":0, \u00XX, base64): a column's bytes are summed in 64 bits
     // BEFORE the 32-bit scan, and a column of 4 GiB or more is refused — the scan would wrap and the text kernels write at wrapped offsets.
-    Buf tot64 = dalloc_zero((size_t)ntext * 8 + 16);
-    sum_u32_segments_u64(ptr<uint32_t>(lens_all), nrows, ntext, seg_stride, ptr<unsigned long long>(tot64));
-    exclusive_scan_u32_segments(ptr<uint32_t>(lens_all), nrows, ntext, seg_stride);
-    const uint32_t *h64 = d2h_u32(tot64->p, (size_t)ntext * 2);
+    text.scan(true);
     tf::sync();
     for (int t = 0; t < ntext; t++) {
-      const uint64_t bytes = (uint64_t)h64[2 * t] | (uint64_t)h64[2 * t + 1] << 32;
-      if (text_total_exceeds(bytes)) return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_sr_proto_parse: column " + db->cols[(size_t)text_cols[(size_t)t]].name + " holds 4 GiB of text or more: split the batch");
+      if (text_total_exceeds(text.total(t))) return tf::fail(TFGPU_ERR_UNSUPPORTED, "tfgpu_sr_proto_parse: column " + db->cols[(size_t)text_cols[(size_t)t]].name + " holds 4 GiB of text or more: split the batch");
     }
     for (int t = 0; t < ntext; t++) {
       DColumn &d = db->cols[(size_t)text_cols[(size_t)t]];
-      d.data_len = (uint64_t)h64[2 * t] | (uint64_t)h64[2 * t + 1] << 32;  // (below 4 GiB, checked above: what the 32-bit scan left at [nrows])
+      d.data_len = text.total(t);  // (below 4 GiB, checked above: what the 32-bit scan left at [nrows])
       d.data = dalloc(d.data_len + 16);
       oc[(size_t)text_cols[(size_t)t]].data = ptr<uint8_t>(d.data);
     }
@@ -397,33 +357,15 @@ extern "C" int tfgpu_sr_proto_parse(const tfgpu_pb_schema *sch, uint32_t schema_
       KernelTimer t("pb_text");
       std::vector<int32_t> copy_cols, any_text, wide_text;
       for (int32_t j : text_cols) (wide(j) ? wide_text : (fl[j].repeated || fl[j].ptype == TFGPU_PB_MESSAGE) ? any_text : copy_cols).push_back(j);
-      if (!copy_cols.empty()) { Buf bc = upload_small(copy_cols.data(), copy_cols.size() * 4); pbd::pb_text_copy<<<dim3(pbd::nblk(nrows, 256), (unsigned)copy_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bc)); }
-      if (!any_text.empty()) { Buf bc = upload_small(any_text.data(), any_text.size() * 4); pbd::pb_text_any<false><<<dim3(pbd::nblk(nrows, 256), (unsigned)any_text.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bc)); }
-      if (!wide_text.empty()) { Buf bc = upload_small(wide_text.data(), wide_text.size() * 4); pbd::pb_text_any<true><<<dim3(pbd::nblk(nrows, 256), (unsigned)wide_text.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bc)); }
+      if (!copy_cols.empty()) { Buf bc = upload_small(copy_cols.data(), copy_cols.size() * 4); pbd::pb_text_copy<<<dim3(grid_for(nrows, 256), (unsigned)copy_cols.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bc)); }
+      if (!any_text.empty()) { Buf bc = upload_small(any_text.data(), any_text.size() * 4); pbd::pb_text_any<false><<<dim3(grid_for(nrows, 256), (unsigned)any_text.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bc)); }
+      if (!wide_text.empty()) { Buf bc = upload_small(wide_text.data(), wide_text.size() * 4); pbd::pb_text_any<true><<<dim3(grid_for(nrows, 256), (unsigned)wide_text.size()), 256, 0, st>>>(p, ptr<pbd::OutCol>(boc), ptr<int32_t>(bc)); }
     }
   }
   // rows whose `any` value holds a NaN / Inf: the reference keeps the Go float inside the map / slice, the column's JSON text cannot
   std::vector<uint32_t> hostm;
   std::unique_ptr<tfgpu_dbatch> result = std::move(db);
-  bool some_host_rows = false;
-  if (has_msg && nrows) {  // almost never: one flag word says so, the per-row marks come down only when it is set
-    const uint32_t *hflag = any_nonzero_to_host(ptr<uint32_t>(host_rows), nrows);
-    tf::sync();
-    some_host_rows = *hflag != 0;
-  }
-  if (some_host_rows) {
-    std::vector<uint32_t> hr((size_t)nrows), rm((size_t)nrows);
-    d2h(hr.data(), host_rows->p, (size_t)nrows * 4); d2h(rm.data(), row_msg->p, (size_t)nrows * 4);
-    tf::sync();
-    bool any = false;
-    std::vector<uint32_t> keepv((size_t)nrows + 1, 0u);
-    for (int64_t r = 0; r < nrows; r++) { if (hr[(size_t)r]) { any = true; hostm.push_back(rm[(size_t)r]); } else keepv[(size_t)r] = 1u; }
-    if (any) {
-      Buf dk = dalloc(keepv.size() * 4 + 16);
-      h2d(dk->p, keepv.data(), keepv.size() * 4);
-      result = tf::compact_rows(*result, dk);
-    }
-  }
+  if (has_msg && nrows) hostm = split_host_rows(result, host_rows, row_msg, nrows);  // almost never
   int64_t ne = 0;
   if (nerr_total || !hostm.empty()) {
     std::vector<uint8_t> hst((size_t)nma);

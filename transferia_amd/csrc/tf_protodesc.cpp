@@ -311,13 +311,6 @@ static std::string base64_decode(const std::string &s) {
 using namespace tf;
 using namespace tf::ppd;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 extern "C" {
 
 int tfgpu_proto_parser_create(const tfgpu_proto_parser_config *c, tfgpu_proto_parser **out) {

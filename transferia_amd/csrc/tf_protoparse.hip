@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "tf_common.hpp"
-#include "tf_rows.hpp"
+#include "tf_ingest.hpp"
 #include "tf_devrow.hpp"
 #include "tf_devfmt.hpp"
 #include "tf_pbwire.hpp"
@@ -384,31 +384,11 @@ __global__ void __launch_bounds__(256) pp_const_text(const uint8_t *text, uint32
   if (i < nrows * (int64_t)tlen) data[i] = text[i % tlen];
 }
 
-template <class T> static const T *stage_array(const void *src, size_t count, int mem, Buf &keep) {
-  if (!src) return nullptr;
-  if (mem == TFGPU_MEM_DEVICE) return reinterpret_cast<const T *>(src);
-  keep = dalloc(count * sizeof(T) + 16);
-  h2d(keep->p, src, count * sizeof(T));
-  return ptr<T>(keep);
-}
-
 }  // namespace ppd
 }  // namespace tf
 
 using namespace tf;
 using namespace tf::ppd;
-
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
-static bool pp_text_total_exceeds(uint64_t bytes) {  // TFGPU_TEST_TEXT_LIMIT (tests only) lowers the bound of a 32-bit-offset column
-  static const uint64_t limit = [] { const char *e = std::getenv("TFGPU_TEST_TEXT_LIMIT"); return e && *e ? (uint64_t)std::strtoull(e, nullptr, 10) : 0xFFFFFFF0ull; }();
-  return bytes >= limit;
-}
 
 extern "C" int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu_message_batch *b, const int64_t *create_time_ns, tfgpu_dbatch **out,
                                         tfgpu_proto_unparsed *unparsed, int64_t cap, int64_t *nunparsed, int64_t *event_base) {
@@ -433,9 +413,8 @@ extern "C" int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu
   for (auto &ch : topic) if (ch == '/' || ch == '@') ch = '_';  // tableName
 
   // ---- the batch in HBM ---------------------------------------------------------------------------------------------------------------------------------
-  Buf vdata = dalloc((size_t)b->values_len + 64), vstart, boffset, bwt, bct;
-  if (b->values_len) { if (b->mem == TFGPU_MEM_DEVICE) d2d(vdata->p, b->values, (size_t)b->values_len); else h2d(vdata->p, b->values, (size_t)b->values_len); }
-  TF_HIP(hipMemsetAsync((char *)vdata->p + b->values_len, 0, 64, st));
+  Buf vdata, vstart, boffset, bwt, bct;
+  stage_bytes(b->values, b->values_len, b->mem, vdata);
   static const uint64_t ZERO1[1] = {0};
   const uint64_t *dstart = n ? stage_array<uint64_t>(b->value_start, (size_t)n + 1, b->mem, vstart) : stage_array<uint64_t>(ZERO1, 1, TFGPU_MEM_HOST, vstart);
   const uint64_t *doffset = stage_array<uint64_t>(b->offset, (size_t)n, b->mem, boffset);
@@ -517,15 +496,13 @@ extern "C" int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu
   std::vector<OutCol> oc((size_t)std::max(ncol, 1));
   std::memset(oc.data(), 0, oc.size() * sizeof(OutCol));
   std::vector<int32_t> text_cols, light_cols, any_cols, wide_cols;
-  const int64_t seg_stride = ((nrows + 1 + 3) / 4) * 4;
   auto is_any = [&](const Col &c) { return c.field >= 0 && (h->fields[(size_t)c.field].repeated || h->fields[(size_t)c.field].ptype == TFGPU_PB_MESSAGE); };
   auto is_wide = [&](const Col &c) { const DField &f = h->fields[(size_t)c.field]; return f.repeated == 2 || (f.repeated && f.ptype == TFGPU_PB_MESSAGE); };
   int ntext = 0;
   bool has_any = false;
   for (auto &c : h->cols) if (c.field >= 0) { const int t = h->fields[(size_t)c.field].ptype; if (is_any(c) || t == TFGPU_PB_STRING || t == TFGPU_PB_BYTES) ntext++; if (is_any(c)) has_any = true; }
-  Buf lens_all = dalloc_zero((size_t)std::max(ntext, 1) * (size_t)seg_stride * 4 + 16);
-  const size_t vbytes = ((size_t)((nra + 63) / 64) * 8 + 8 + 63) & ~(size_t)63;
-  Buf valid_all = dalloc_zero((size_t)std::max(ncol, 1) * vbytes);
+  TextSegments text(ntext, nrows);
+  const ValidityBlock valid(ncol, nrows);
   Aux ax{};
   ax.row_ev = p.row_ev; ax.ev_msg = p.ev_msg; ax.ev_idx = p.ev_idx; ax.nrows = nrows; ax.offset = doffset; ax.wt = dwt; ax.ct = dct;
   bool has_aux = false;
@@ -543,7 +520,7 @@ extern "C" int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu
         case AUX_PARTITION: {
           d.repr = TFGPU_R_STRING;
           d.data_len = (uint64_t)nrows * partition_text.size();
-          if (pp_text_total_exceeds(d.data_len)) return tf::fail(TFGPU_ERR_UNSUPPORTED, std::string(T) + "column _partition holds 4 GiB of text or more: split the batch");
+          if (text_total_exceeds(d.data_len)) return tf::fail(TFGPU_ERR_UNSUPPORTED, std::string(T) + "column _partition holds 4 GiB of text or more: split the batch");
           d.offsets = dalloc((size_t)(nrows + 1) * 4 + 16); d.data = dalloc((size_t)d.data_len + 16);
           Buf bt = upload_const(partition_text.data(), partition_text.size());
           pp_const_text<<<grid_for(std::max<int64_t>(nrows + 1, (int64_t)d.data_len), 256), 256, 0, st>>>(ptr<uint8_t>(bt), (uint32_t)partition_text.size(), nrows, ptr<uint32_t>(d.offsets), ptr<uint8_t>(d.data));
@@ -571,12 +548,12 @@ extern "C" int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu
       }
     }
     if (c.field >= 0 && !d.values) {
-      d.offsets = subbuf(lens_all, (size_t)ti * (size_t)seg_stride * 4, (size_t)(nrows + 1) * 4);
-      o.lens = ptr<uint32_t>(d.offsets);
+      d.offsets = text.offsets(ti);
+      o.lens = text.seg(ti);
       text_cols.push_back(j);
       ti++;
     }
-    if (c.field >= 0) { d.validity = subbuf(valid_all, (size_t)j * vbytes, (size_t)((nra + 63) / 64) * 8 + 8); o.validity = ptr<uint8_t>(d.validity); }
+    if (c.field >= 0) { d.validity = valid.col(j); o.validity = ptr<uint8_t>(d.validity); }
     db->schema.push_back({d.name, d.dtype});
     if (c.flags & TFGPU_COL_KEY) db->key_names.push_back(c.name);
     db->cols.push_back(std::move(d));
@@ -591,15 +568,12 @@ extern "C" int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu
     if (!wide_cols.empty()) { Buf l = list(wide_cols); pp_cells<true, true><<<dim3(grid_for(nrows, 256), (unsigned)wide_cols.size()), 256, 0, st>>>(p, ptr<OutCol>(boc), ptr<int32_t>(l), ptr<uint32_t>(host_rows)); }
   }
   if (ntext) {
-    Buf t64 = dalloc_zero((size_t)ntext * 8 + 16);
-    sum_u32_segments_u64(ptr<uint32_t>(lens_all), nrows, ntext, seg_stride, ptr<unsigned long long>(t64));
-    exclusive_scan_u32_segments(ptr<uint32_t>(lens_all), nrows, ntext, seg_stride);
-    const uint32_t *h64 = d2h_u32(t64->p, (size_t)ntext * 2);
+    text.scan(true);
     tf::sync();
     for (int t = 0; t < ntext; t++) {
-      const uint64_t bytes = (uint64_t)h64[2 * t] | (uint64_t)h64[2 * t + 1] << 32;
+      const uint64_t bytes = text.total(t);
       DColumn &d = db->cols[(size_t)text_cols[(size_t)t]];
-      if (pp_text_total_exceeds(bytes)) return tf::fail(TFGPU_ERR_UNSUPPORTED, std::string(T) + "column " + d.name + " holds 4 GiB of text or more: split the batch");
+      if (text_total_exceeds(bytes)) return tf::fail(TFGPU_ERR_UNSUPPORTED, std::string(T) + "column " + d.name + " holds 4 GiB of text or more: split the batch");
       d.data_len = bytes;
       d.data = dalloc((size_t)d.data_len + 16);
       oc[(size_t)text_cols[(size_t)t]].data = ptr<uint8_t>(d.data);
@@ -618,22 +592,8 @@ extern "C" int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu
 
   // ---- rows for the host (a NaN / Inf inside an `any`, −0.0 under NotFillEmptyFields), the failed events ------------------------------------------------
   std::unique_ptr<tfgpu_dbatch> result = std::move(db);
-  bool some_host_rows = false;
-  if (nrows && (has_any || h->not_fill_empty)) {
-    const uint32_t *hflag = any_nonzero_to_host(ptr<uint32_t>(host_rows), nrows);
-    tf::sync();
-    some_host_rows = *hflag != 0;
-  }
   std::vector<uint32_t> host_events;
-  if (some_host_rows) {
-    std::vector<uint32_t> hr((size_t)nrows), re((size_t)nrows), keepv((size_t)nrows + 1, 0u);
-    d2h(hr.data(), host_rows->p, (size_t)nrows * 4); d2h(re.data(), row_ev->p, (size_t)nrows * 4);
-    tf::sync();
-    for (int64_t r = 0; r < nrows; r++) { if (hr[(size_t)r]) host_events.push_back(re[(size_t)r]); else keepv[(size_t)r] = 1u; }
-    Buf dk = dalloc(keepv.size() * 4 + 16);
-    h2d(dk->p, keepv.data(), keepv.size() * 4);
-    result = tf::compact_rows(*result, dk);
-  }
+  if (nrows && (has_any || h->not_fill_empty)) host_events = split_host_rows(result, host_rows, row_ev, nrows);
   std::vector<uint32_t> hbase((size_t)n + 1, 0u);
   if (event_base || nerr_total || !host_events.empty()) {
     if (n) d2h(hbase.data(), nfin->p, (size_t)(n + 1) * 4);

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "tf_plan.hpp"
+#include "tf_ingest.hpp"
 #include "tf_devrow.hpp"
 #include "tf_devfmt.hpp"
 #include "tf_jsonscan.hpp"
@@ -360,30 +361,13 @@ struct Staged {
   const uint64_t *d_offset = nullptr, *d_pstart = nullptr; const int64_t *d_wt = nullptr;
   const tfgpu_header_pair *d_pairs = nullptr; const uint8_t *d_hnil = nullptr, *d_hdata = nullptr;
 };
-// an array of the batch in HBM: a host array is copied, a device array is used where it is
-template <class T> static const T *stage_array(const void *src, size_t count, int mem, Buf &keep) {
-  if (!src) return nullptr;
-  if (mem == TFGPU_MEM_DEVICE) return reinterpret_cast<const T *>(src);
-  keep = dalloc(count * sizeof(T) + 16);
-  h2d(keep->p, src, count * sizeof(T));
-  return ptr<T>(keep);
-}
-// a byte buffer: always a copy of our own with 64 zero bytes behind it (the scanners and the segmented copy read whole aligned words)
-static const uint8_t *stage_bytes(const void *src, uint64_t len, int mem, Buf &keep) {
-  keep = dalloc((size_t)len + 64);
-  if (len) { if (mem == TFGPU_MEM_DEVICE) d2d(keep->p, src, (size_t)len); else h2d(keep->p, src, (size_t)len); }
-  TF_HIP(hipMemsetAsync((char *)keep->p + len, 0, 64, ctx().stream));
-  return ptr<uint8_t>(keep);
-}
 
 struct TableJob {  // one of the two result tables while it is built
   bool dlq; Buf rows; int64_t nrows = 0;
   bool ts, hd, key; int kt, vt;
   std::unique_ptr<tfgpu_dbatch> db;
-  Buf lens; int64_t stride = 0; int nseg = 0;
+  TextSegments text; int nseg = 0;  // the scanned columns of the table
   int seg_headers = -1, seg_key = -1, seg_val = -1, seg_reason = -1;
-  Buf totals;  // u64 [nseg]
-  const uint32_t *h_totals = nullptr;
 };
 
 }  // namespace rawtt
@@ -391,13 +375,6 @@ struct TableJob {  // one of the two result tables while it is built
 
 using namespace tf;
 using namespace tf::rawtt;
-
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
 
 static uint32_t long_bytes_now() {  // TFGPU_RAWTT_LONG_BYTES: measurement runs move the short / long switch (tools/rawtable_bench.py)
   const char *e = std::getenv("TFGPU_RAWTT_LONG_BYTES");
@@ -610,10 +587,8 @@ int tfgpu_raw_to_table_parse(const tfgpu_raw_to_table *h, const tfgpu_message_ba
     if (j.key) j.seg_key = j.nseg++;
     j.seg_val = j.nseg++;
     if (j.dlq) j.seg_reason = j.nseg++;
-    j.stride = ((nr + 1 + 3) / 4) * 4;
-    j.lens = dalloc_zero((size_t)j.stride * (size_t)j.nseg * 4 + 16);
-    j.totals = dalloc_zero((size_t)j.nseg * 8);
-    auto seg = [&](int sgi) { return ptr<uint32_t>(j.lens) + (int64_t)sgi * j.stride; };
+    j.text = TextSegments(j.nseg, nr);
+    auto seg = [&](int sgi) { return j.text.seg(sgi); };
     col("offset").values = dalloc((size_t)nra * 4); col("partition").values = dalloc((size_t)nra * 4);
     if (j.ts) { col("timestamp").values = dalloc((size_t)nra * 8); col("timestamp").nanos = dalloc((size_t)nra * 4); }
     if (!nr) continue;
@@ -649,9 +624,7 @@ int tfgpu_raw_to_table_parse(const tfgpu_raw_to_table *h, const tfgpu_message_ba
     };
     if (j.key && j.kt == RT_JSON && s.key.start) any_len(s.key, kinfo, j.seg_key);
     if (j.vt == RT_JSON) any_len(s.val, vinfo, j.seg_val);
-    sum_u32_segments_u64(ptr<uint32_t>(j.lens), nr, j.nseg, j.stride, reinterpret_cast<unsigned long long *>(j.totals->p));
-    exclusive_scan_u32_segments(ptr<uint32_t>(j.lens), nr, j.nseg, j.stride);
-    j.h_totals = d2h_u32(j.totals->p, (size_t)j.nseg * 2);
+    j.text.scan(true);
   }
   tf::sync();
   for (TableJob &j : jobs) {
@@ -659,12 +632,11 @@ int tfgpu_raw_to_table_parse(const tfgpu_raw_to_table *h, const tfgpu_message_ba
     const int64_t nr = j.nrows;
     const int32_t *rows = ptr<int32_t>(j.rows);
     auto col = [&](const char *name) -> DColumn & { for (auto &c : db.cols) if (c.name == name) return c; throw Error(TFGPU_ERR_INVALID, "raw_to_table: no such column"); };
-    auto total = [&](int sgi) -> uint64_t { if (!nr) return 0; uint64_t v; std::memcpy(&v, j.h_totals + 2 * sgi, 8); return v; };
     auto text = [&](const char *name, int sgi) -> DColumn & {
       DColumn &c = col(name);
-      if (total(sgi) >= 0xFFFFFFF0ull) throw Error(TFGPU_ERR_UNSUPPORTED, std::string(T) + "column " + name + " of table " + db.table + " reaches 4 GiB of text (32-bit offsets): split the batch");
-      c.offsets = subbuf(j.lens, (size_t)sgi * (size_t)j.stride * 4, (size_t)(nr + 1) * 4);
-      c.data_len = total(sgi);
+      if (text_total_exceeds(j.text.total(sgi))) throw Error(TFGPU_ERR_UNSUPPORTED, std::string(T) + "column " + name + " of table " + db.table + " reaches 4 GiB of text (32-bit offsets): split the batch");
+      c.offsets = j.text.offsets(sgi);
+      c.data_len = j.text.total(sgi);
       c.data = dalloc((size_t)c.data_len + 16);
       return c;
     };

@@ -280,13 +280,6 @@ Buf validity_minus_absent(const Buf &validity, const Buf &absent, int64_t nrows)
 
 using namespace tf;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 extern "C" {
 
 int tfgpu_abi_version(void) { return TFGPU_ABI_VERSION; }

@@ -340,13 +340,6 @@ void dbatch_drop_src_row(tfgpu_dbatch *b) { if (b) b->src_row = nullptr; }
 
 using namespace tf;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 extern "C" {
 
 int tfgpu_dbatch_slice(const tfgpu_dbatch *b, int64_t row0, int64_t nrows, tfgpu_dbatch **out) {

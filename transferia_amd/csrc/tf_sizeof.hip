@@ -116,13 +116,6 @@ __global__ void __launch_bounds__(256) deepsizeof_rows(const SzCol *cols, int nc
 
 }  // namespace
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 extern "C" int tfgpu_dbatch_deepsizeof(const tfgpu_dbatch *in, uint32_t flags, uint64_t *per_row, uint64_t *total) {
   TF_API_BEGIN
   tf::dense(in, true);  // its rows may still be a selection (tfgpu_dbatch::pending); a row's ColumnValues hold the columns it lists

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "tf_ingest.hpp"
 #include "tf_jsonscan.hpp"
 #include "tf_segcopy.hpp"
 #include "tf_jsontile.hpp"
@@ -679,40 +680,22 @@ __global__ void __launch_bounds__(256) sr_pack_absent(Params p, const int32_t *o
   if (v) atomicOr(&colflag[k], 1u);
 }
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
-
 // input bytes + message starts in HBM, frames counted and listed; returns the frame count
 struct Staged {
-  Buf bytes, ms, fcount, frames, first, nozero;
+  Buf bytes, fcount, frames, first, nozero;
+  MessageStarts ms;
   Params p{};
   int64_t nframes = 0;
 };
 static void stage_frames(Staged &s, const void *bytes, uint64_t len, int mem, const tfgpu_messages *msgs) {
   Context &cx = ctx();
   hipStream_t st = cx.stream;
-  if (len >= 0xFFFFFFF0ull) throw Error(TFGPU_ERR_UNSUPPORTED, "confluent SR: batch must be < 4 GiB (32-bit offsets)");
-  if (mem == TFGPU_MEM_HOST) {
-    s.bytes = dalloc(len + 64);
-    h2d(s.bytes->p, bytes, len);
-    TF_HIP(hipMemsetAsync((char *)s.bytes->p + len, 0, 64, st));
-    s.p.data = ptr<uint8_t>(s.bytes);
-  } else {
-    s.p.data = (const uint8_t *)bytes;
-    if (reinterpret_cast<uintptr_t>(s.p.data) & 15) throw Error(TFGPU_ERR_INVALID, "confluent SR: device buffer must be 16-byte aligned");
-  }
+  s.p.data = stage_input(bytes, len, mem, "confluent SR", s.bytes);
   const int64_t nmsg = msgs ? msgs->nmsg : 1;
   if (nmsg < 0 || (msgs && nmsg > 0 && !msgs->start)) throw Error(TFGPU_ERR_INVALID, "confluent SR: bad message batch");
-  std::vector<uint32_t> ms((size_t)nmsg + 1);
-  if (msgs) {
-    for (int64_t m = 0; m <= nmsg; m++) {
-      if (msgs->start[m] > len || (m && msgs->start[m] < msgs->start[m - 1])) throw Error(TFGPU_ERR_INVALID, "confluent SR: message offsets must be ascending and inside the buffer");
-      ms[(size_t)m] = (uint32_t)msgs->start[m];
-    }
-  } else { ms[0] = 0; ms[1] = (uint32_t)len; }
-  s.ms = dalloc(ms.size() * 4 + 16);
-  h2d(s.ms->p, ms.data(), ms.size() * 4);
+  s.ms = stage_message_starts(msgs, len, "confluent SR");
   s.fcount = dalloc_zero((size_t)(nmsg + 1) * 4 + 16);
-  s.p.ms = ptr<uint32_t>(s.ms); s.p.nmsg = nmsg; s.p.fcount = ptr<uint32_t>(s.fcount);
+  s.p.ms = ptr<uint32_t>(s.ms.dev); s.p.nmsg = nmsg; s.p.fcount = ptr<uint32_t>(s.fcount);
   s.first = dalloc((size_t)std::max<int64_t>(nmsg, 1) * sizeof(tfgpu_sr_frame));
   const tfgpu_sr_frame *first = reinterpret_cast<const tfgpu_sr_frame *>(s.first->p);
   s.nozero = dalloc_zero((size_t)std::max<int64_t>(nmsg, 1) + 16);
@@ -720,7 +703,7 @@ static void stage_frames(Staged &s, const void *bytes, uint64_t len, int mem, co
     KernelTimer t("sr_frames");
     sr_find_zero<<<(unsigned)((nmsg + 3) / 4), 256, 0, st>>>(s.p, ptr<uint8_t>(s.nozero));
     s.p.nozero = ptr<uint8_t>(s.nozero);
-    sr_count_frames<<<nblk(nmsg, 256), 256, 0, st>>>(s.p, reinterpret_cast<tfgpu_sr_frame *>(s.first->p));
+    sr_count_frames<<<grid_for(nmsg, 256), 256, 0, st>>>(s.p, reinterpret_cast<tfgpu_sr_frame *>(s.first->p));
   }
   exclusive_scan_u32(s.p.fcount, s.p.fcount, nmsg, true);
   const uint32_t *h = d2h_u32(s.p.fcount + nmsg);
@@ -728,7 +711,7 @@ static void stage_frames(Staged &s, const void *bytes, uint64_t len, int mem, co
   s.nframes = *h;
   s.frames = dalloc((size_t)std::max<int64_t>(s.nframes, 1) * sizeof(tfgpu_sr_frame));
   s.p.frames = reinterpret_cast<tfgpu_sr_frame *>(s.frames->p); s.p.nframes = s.nframes;
-  if (nmsg && s.nframes) { KernelTimer t("sr_frames"); sr_fill_frames<<<nblk(nmsg, 256), 256, 0, st>>>(s.p, first); }
+  if (nmsg && s.nframes) { KernelTimer t("sr_frames"); sr_fill_frames<<<grid_for(nmsg, 256), 256, 0, st>>>(s.p, first); }
 }
 
 struct LastFrames { const tfgpu_sr_frame *host = nullptr; int64_t n = -1; const void *bytes = nullptr; Buf dev; };
@@ -738,13 +721,6 @@ static thread_local LastFrames g_last;
 }  // namespace tf
 
 using namespace tf;
-
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
 
 extern "C" int tfgpu_sr_frames(const void *bytes, uint64_t len, int mem, const tfgpu_messages *msgs, tfgpu_sr_frame *frames, int64_t cap, int64_t *nframes) {
   TF_API_BEGIN
@@ -816,13 +792,13 @@ extern "C" int tfgpu_sr_json_parse(const tfgpu_sr_json_options *o, const void *b
         bival = dalloc((size_t)std::max(np, 1) * (size_t)nfa * 8 + 16);
         p.ival = ptr<int64_t>(bival);
         { KernelTimer t("sr_quick_map"); sr::sr_quick_map<<<1, JQ_THREADS, 0, st>>>(p, ptr<sr::SrqMap>(bmap)); }
-        { KernelTimer t("sr_parse_quick"); sr::sr_parse_quick<<<sr::nblk(nf, qper), JQ_THREADS, 0, st>>>(p, ptr<sr::SrqMap>(bmap), qper, ptr<int64_t>(bival), ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1, ablate); }
+        { KernelTimer t("sr_parse_quick"); sr::sr_parse_quick<<<grid_for(nf, qper), JQ_THREADS, 0, st>>>(p, ptr<sr::SrqMap>(bmap), qper, ptr<int64_t>(bival), ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1, ablate); }
       } else {
-      const unsigned ntile = sr::nblk(nf, per_tile), nb = (unsigned)std::min<int64_t>((int64_t)ntile, (int64_t)cx.num_cus * 2);
+      const unsigned ntile = grid_for(nf, per_tile), nb = (unsigned)std::min<int64_t>((int64_t)ntile, (int64_t)cx.num_cus * 2);
       { KernelTimer t("sr_parse_tiles");
         sr::sr_parse_tiles<<<nb, JT_THREADS, 0, st>>>(p, per_tile, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1, ablate); }
       }
-      { KernelTimer t("sr_parse_frames"); sr::sr_parse_listed<<<sr::nblk(nf, 128), 128, 0, st>>>(p, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
+      { KernelTimer t("sr_parse_frames"); sr::sr_parse_listed<<<grid_for(nf, 128), 128, 0, st>>>(p, ptr<uint32_t>(slow), ptr<uint32_t>(slow) + 1); }
       static const bool dbg = [] { const char *e = std::getenv("TFGPU_JSON_TILE_DEBUG"); return e && e[0] == '1'; }();
       if (dbg) {
         const uint32_t *a = d2h_u32(slow->p);
@@ -830,8 +806,8 @@ extern "C" int tfgpu_sr_json_parse(const tfgpu_sr_json_options *o, const void *b
         std::fprintf(stderr, "[tfgpu] sr tiles: %lld frames, %d per tile, %u to parse_frame\n", (long long)nf, (int)used_per_tile, *a);
       }
     } else
-    { KernelTimer t("sr_parse_frames"); sr::sr_parse_frames<<<sr::nblk(nf, 128), 128, 0, st>>>(p); }
-    { KernelTimer t("sr_message_rule"); sr::sr_message_rule<<<sr::nblk(p.nmsg, 256), 256, 0, st>>>(p); }
+    { KernelTimer t("sr_parse_frames"); sr::sr_parse_frames<<<grid_for(nf, 128), 128, 0, st>>>(p); }
+    { KernelTimer t("sr_message_rule"); sr::sr_message_rule<<<grid_for(p.nmsg, 256), 256, 0, st>>>(p); }
   }
   exclusive_scan_u32(p.keep, p.keep, nf, true);
   const uint32_t *hrows = d2h_u32(p.keep + nf), *hnerr = d2h_u32(p.nerr);
@@ -847,11 +823,10 @@ extern "C" int tfgpu_sr_json_parse(const tfgpu_sr_json_options *o, const void *b
   p.row_frame = ptr<uint32_t>(row_frame); p.nrows = nrows;
   std::vector<sr::OutCol> oc((size_t)np);
   std::vector<int32_t> text_cols;
-  const int64_t seg_stride = ((nrows + 1 + 3) / 4) * 4;
   int ntext = 0;
   bool has_any = false;
   for (int j = 0; j < np; j++) { if (o->props[j].json_type >= TFGPU_SRT_NUMBER) ntext++; if (o->props[j].json_type == TFGPU_SRT_ANY) has_any = true; }
-  Buf lens_all = dalloc_zero((size_t)std::max(ntext, 1) * (size_t)seg_stride * 4 + 16);
+  TextSegments text(ntext, nrows);
   Buf valid8 = dalloc((size_t)std::max(np, 1) * (size_t)nra);
   int ti = 0;
   for (int j = 0; j < np; j++) {
@@ -871,8 +846,8 @@ extern "C" int tfgpu_sr_json_parse(const tfgpu_sr_json_options *o, const void *b
       default: d.dtype = TFGPU_T_ANY; d.repr = TFGPU_R_JSON;
     }
     if (pr.json_type >= TFGPU_SRT_NUMBER) {
-      d.offsets = subbuf(lens_all, (size_t)ti * (size_t)seg_stride * 4, (size_t)(nrows + 1) * 4);
-      c.lens = ptr<uint32_t>(d.offsets);
+      d.offsets = text.offsets(ti);
+      c.lens = text.seg(ti);
       text_cols.push_back(j);
       ti++;
     }
@@ -884,13 +859,13 @@ extern "C" int tfgpu_sr_json_parse(const tfgpu_sr_json_options *o, const void *b
   }
   Buf boc = upload_small(oc.data(), std::max<size_t>(oc.size(), 1) * sizeof(sr::OutCol));
   if (nrows) {
-    sr::sr_row_frames<<<sr::nblk(nf, 256), 256, 0, st>>>(p);
+    sr::sr_row_frames<<<grid_for(nf, 256), 256, 0, st>>>(p);
     if (np) {
       KernelTimer t("sr_cell_values");
-      sr::sr_cell_values<false><<<dim3(sr::nblk(nrows, 256 * TF_SR_VALUES_RPT), (unsigned)np), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id));
-      if (has_any) sr::sr_cell_values<true><<<dim3(sr::nblk(nrows, 256 * TF_SR_VALUES_RPT), (unsigned)np), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id));
+      sr::sr_cell_values<false><<<dim3(grid_for(nrows, 256 * TF_SR_VALUES_RPT), (unsigned)np), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id));
+      if (has_any) sr::sr_cell_values<true><<<dim3(grid_for(nrows, 256 * TF_SR_VALUES_RPT), (unsigned)np), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(db->src_row), ptr<uint32_t>(db->part_id));
     }
-    if (np) sr::sr_pack_validity<<<sr::nblk((int64_t)np * ((nrows + 7) / 8), 256), 256, 0, st>>>(ptr<sr::OutCol>(boc), np, nrows);
+    if (np) sr::sr_pack_validity<<<grid_for((int64_t)np * ((nrows + 7) / 8), 256), 256, 0, st>>>(ptr<sr::OutCol>(boc), np, nrows);
   }
   if (np == 0 && nrows) return tf::fail(TFGPU_ERR_UNSUPPORTED, "confluent SR json: a schema without properties");
   // isGenerateUpdates: every item is an Update, and lists the optional fields its payload holds
@@ -905,23 +880,22 @@ extern "C" int tfgpu_sr_json_parse(const tfgpu_sr_json_options *o, const void *b
       std::vector<uint8_t *> bp;
       for (size_t k = 0; k < optp.size(); k++) { optbits.push_back(dalloc((size_t)((nra + 7) / 8) + 8)); bp.push_back(ptr<uint8_t>(optbits.back())); }
       Buf bopt = upload_small(optp.data(), optp.size() * 4), bbp = upload_small(bp.data(), bp.size() * sizeof(uint8_t *)), colflag = dalloc_zero(optp.size() * 4);
-      sr::sr_pack_absent<<<sr::nblk((int64_t)optp.size() * ((nrows + 7) / 8), 256), 256, 0, st>>>(p, ptr<int32_t>(bopt), (int)optp.size(), ptr<uint8_t *>(bbp), ptr<uint32_t>(colflag));
+      sr::sr_pack_absent<<<grid_for((int64_t)optp.size() * ((nrows + 7) / 8), 256), 256, 0, st>>>(p, ptr<int32_t>(bopt), (int)optp.size(), ptr<uint8_t *>(bbp), ptr<uint32_t>(colflag));
       habs = d2h_u32(colflag->p, optp.size());  // read at the next sync: a column no row leaves out carries no bitmap
     }
   }
   if (ntext) {
-    exclusive_scan_u32_segments(ptr<uint32_t>(lens_all), nrows, ntext, seg_stride);  // offsets in place, the total at [nrows]
-    const uint32_t *tot = segment_totals_to_host(ptr<uint32_t>(lens_all), nrows, ntext, seg_stride);
+    text.scan(false);  // offsets in place, the totals on their way down
     // OFF by default: measured on the MI355X (gpurun r07b, 2^18 hits messages) sr_cell_text is 0.60 ms one lane per cell and 0.65 ms this way —
     // a third of the text (Cyrillic titles, strings with escapes) is not VT_PLAIN and still takes the walkers, and the marking pass re-reads the value records
     static const bool words = [] { const char *e = std::getenv("TFGPU_SR_COPY_WORDS"); return e && e[0] == '1'; }();
     Buf spec = dalloc_zero((size_t)ntext * 4), btc0 = upload_small(text_cols.data(), text_cols.size() * 4);
-    if (nrows && words) sr::sr_mark_special<<<dim3(sr::nblk(nrows, 256 * 16), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc0), ptr<uint32_t>(spec));
+    if (nrows && words) sr::sr_mark_special<<<dim3(grid_for(nrows, 256 * 16), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc0), ptr<uint32_t>(spec));
     const uint32_t *hspec = d2h_u32(spec->p, (size_t)ntext);
     tf::sync();
     for (int t = 0; t < ntext; t++) {
       DColumn &d = db->cols[(size_t)text_cols[(size_t)t]];
-      d.data_len = tot[t];
+      d.data_len = text.total(t);
       d.data = dalloc(d.data_len + 8);
       oc[(size_t)text_cols[(size_t)t]].data = ptr<uint8_t>(d.data);
     }
@@ -930,12 +904,12 @@ extern "C" int tfgpu_sr_json_parse(const tfgpu_sr_json_options *o, const void *b
     if (nrows) {
       KernelTimer t("sr_cell_text");
       if (words) {
-        sr::sr_copy_words<<<dim3(sr::nblk(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc));
+        sr::sr_copy_words<<<dim3(grid_for(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc));
         std::vector<int32_t> sp;  // the columns that hold cells the walkers write
         for (int t2 = 0; t2 < ntext; t2++) if (hspec[t2]) sp.push_back(text_cols[(size_t)t2]);
-        if (!sp.empty()) { Buf bsp = upload_small(sp.data(), sp.size() * 4); sr::sr_cell_text<false><<<dim3(sr::nblk(nrows, 256), (unsigned)sp.size()), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(bsp), (int32_t)sp.size(), 1); }
-      } else sr::sr_cell_text<false><<<dim3(sr::nblk(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc), ntext, 0);
-      if (has_any) sr::sr_cell_text<true><<<dim3(sr::nblk(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc), ntext, 0);
+        if (!sp.empty()) { Buf bsp = upload_small(sp.data(), sp.size() * 4); sr::sr_cell_text<false><<<dim3(grid_for(nrows, 256), (unsigned)sp.size()), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(bsp), (int32_t)sp.size(), 1); }
+      } else sr::sr_cell_text<false><<<dim3(grid_for(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc), ntext, 0);
+      if (has_any) sr::sr_cell_text<true><<<dim3(grid_for(nrows, 256), (unsigned)ntext), 256, 0, st>>>(p, ptr<sr::OutCol>(boc), ptr<int32_t>(btc), ntext, 0);
     }
   }
   // ---- frames the reference turns into `_unparsed` items / rows for the stock path ----

@@ -10,13 +10,6 @@
 
 using namespace tf;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 namespace tf {
 
 __global__ void fill_row_index(uint64_t *out, const uint32_t *rank, int64_t n, uint64_t base) {

@@ -393,13 +393,6 @@ static std::unique_ptr<tfgpu_tablesplit> split_batch(const tfgpu_plan &p, std::u
 
 using namespace tf;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 static int check_handle(const tfgpu_tablesplit *s, int32_t t, bool need_table, const char *what) {
   if (!s) return tf::fail(TFGPU_ERR_INVALID, std::string(what) + ": null handle");
   if (need_table && (t < 0 || (size_t)t >= s->ntables())) return tf::fail(TFGPU_ERR_INVALID, std::string(what) + ": table index out of range");

@@ -16,13 +16,6 @@
 
 using namespace tf;
 
-#define TF_API_BEGIN try {
-#define TF_API_END                                                        \
-  }                                                                       \
-  catch (const tf::Error &e) { return tf::fail(e.code, e.what()); }       \
-  catch (const std::bad_alloc &) { return tf::fail(TFGPU_ERR_NOMEM, "out of host memory"); } \
-  catch (const std::exception &e) { return tf::fail(TFGPU_ERR_INVALID, e.what()); }
-
 struct tfgpu_transformation {
   std::vector<const tfgpu_plan *> transformers;  // config order, then ExtraTransformers (middlewares/transformation.go:15-22)
   std::vector<tfgpu_plan *> owned;                // plans built here from the transfer's config (tfgpu_transformation_from_config)
