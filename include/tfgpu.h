@@ -1462,6 +1462,84 @@ typedef struct tfgpu_proto_unparsed { int64_t event; int64_t msg; uint64_t start
 int tfgpu_proto_parser_parse(const tfgpu_proto_parser *h, const tfgpu_message_batch *batch, const int64_t *create_time_ns, tfgpu_dbatch **out,
                              tfgpu_proto_unparsed *unparsed, int64_t cap, int64_t *nunparsed, int64_t *event_base);
 
+/* ---- native parser ingest (pkg/parsers/registry/native: abstract.UnmarshalChangeItems, pkg/abstract/restore.go:344-373) -----------------------
+ * The reading side of TFGPU_QFMT_NATIVE: a message value is one JSON array of ChangeItem objects (ChangeItem.UnmarshalJSON, change_item.go:618-678:
+ * the members id, nextlsn, commitTime, txPosition, kind, schema, table, part, columnnames, columnvalues, table_schema, oldkeys, tx_id, query by their
+ * exact names; other members are skipped; numbers are json.Number), checked by ValidateChangeItems and restored cell by cell by abstract.Restore
+ * under the DataType / OriginalType of the column found BY NAME in the item's table_schema (a later schema column of the same name stands).
+ *
+ * ALL OR NOTHING per message, as the reference: the device either parses every item of a message or leaves the whole message to the stock parser
+ * (TFGPU_ROW_HOST_FALLBACK) with a reason, the first offending item and its column; no item of such a message is in any batch.  The device never
+ * declares a message bad: the stock parser gives the reference's own error or result for it.
+ *
+ * Items that agree on schema, table, part (the decoded strings) and on the TEXT of columnnames, table_schema, oldkeys.keynames and oldkeys.keytypes
+ * form one group; groups are numbered by first appearance among the parsed items, rows inside a group follow item order.  A group is an ordinary
+ * batch — namespace, table, TableSchema names / DataTypes / keys, the columns in columnnames order, kinds, OldKeys columns with old_keys_present (bit r:
+ * the row carries keyvalues) — plus what a batch cannot say: `part`, oldkeys.keytypes, the full TableSchema (tfgpu_native_parsed_group_schema: every
+ * tfgpu_colschema field; properties_json and table_schema_json are the message's own text) and a DEVICE-resident tfgpu_row_meta with one entry per
+ * row (id, lsn, commit_time, counter, tx_id, query, names_form; the handle owns it).  Because the group key holds the columnnames text no group has
+ * ABSENT cells or col_order; `"columnnames":null` is names_form 1 (a group without value columns), `[]` is names_form 2.  Batch, meta, part, key
+ * types and schema are directly usable as inputs of tfgpu_queue_serialize (TFGPU_QFMT_NATIVE) and tfgpu_apply_meta.
+ *
+ * Cells the device takes (everything else is a fallback reason): JSON null under any DataType = nil; intN / uintN: a literal -?digits that fits the
+ * type; double / float: a number literal, kept as json.Number (TFGPU_R_JSONNUM); boolean: true / false; utf8 / string: a JSON string, unescaped as
+ * encoding/json does — base64-decoded to TFGPU_R_BYTES under pg:bytea, ydb:String, mysql:binary*, mysql:blob* and IsMysqlBinaryType; date / datetime /
+ * timestamp: a string YYYY-MM-DDThh:mm:ss[.f{1,9}]Z (TFGPU_R_TIME); interval: an integer literal ParseInt takes (TFGPU_R_DURATION); any: a non-string
+ * value re-marshalled as raw_to_table does it (compact, members in key order, number literals kept; TFGPU_R_JSON) unless the OriginalType starts with
+ * mongo:bson, and a JSON string (its json.Marshal text) when the OriginalType is mysql:json, starts with ch:Decimal( / ch:Nullable(Decimal( or starts
+ * with pg: but not pg:timestamp; a string element of an array counts as a string (Restore recurses into []any).  OldKeys values are restored on
+ * Update and Delete items only; an Insert that carries keyvalues is a fallback.
+ * An `any` cell is written as tfgpu_raw_to_table_parse and tfgpu_sr_json_parse write theirs: json.Marshal's DEFAULT text, in which `<`, `>`, `&`, U+2028
+ * and U+2029 inside strings are the escapes \u003c … — the bytes ChangeItem.MarshalJSON puts on the wire, so the native queue format copies the cell
+ * back unchanged.  (The Debezium emitter's note above describes `any` values as unescaped; both spell the same JSON value.)
+ * Values that arrive in HBM (mem = DEVICE) are copied once into a padded block of the library's own, as the other message ingests do: the
+ * scanners read whole words past a message's end.  While the call runs the input is in HBM twice.                                                */
+typedef enum tfgpu_native_reason {
+  TFGPU_NATIVE_OK = 0,
+  TFGPU_NATIVE_SYNTAX = 1,          /* the message is not `[` objects `]` between white space, or an item is not valid JSON                      */
+  TFGPU_NATIVE_UTF8 = 2,            /* an item holds bytes that are not valid UTF-8                                                           */
+  TFGPU_NATIVE_DEPTH = 3,           /* nesting deeper than the scanner follows (128 containers; 16 under an `any` value whose keys are unsorted)  */
+  TFGPU_NATIVE_KEY_FORM = 4,        /* a member key of the item / of oldkeys written with escapes or bytes beyond ASCII                          */
+  TFGPU_NATIVE_DUP_MEMBER = 5,      /* a top-level member (or a member of oldkeys) repeated                                                    */
+  TFGPU_NATIVE_HEADER_VALUE = 6,    /* a fixed member whose value is not of the form its Go field decodes without error or conversion            */
+  TFGPU_NATIVE_KIND = 7,            /* an item of a non-row kind                                                                                */
+  TFGPU_NATIVE_LENGTHS = 8,         /* names and values of different lengths (ValidateChangeItems; keynames / keyvalues on Update and Delete)   */
+  TFGPU_NATIVE_INSERT_KEYVALUES = 9,/* an Insert that carries oldkeys.keyvalues (they are not restored)                                       */
+  TFGPU_NATIVE_SCHEMA_DIFFERS = 10, /* table_schema differs from an earlier item of the same schema and table in its message (Restore reads the FIRST) */
+  TFGPU_NATIVE_SCHEMA_COLUMN = 11,  /* a name the table_schema lacks, a DataType that is none of the ABI's, a table_schema the host does not read   */
+  TFGPU_NATIVE_INT_FORM = 12,       /* a fraction, an exponent or an out-of-range number in an integer or interval column                       */
+  TFGPU_NATIVE_NUM_STRING = 13,     /* a string in a numeric column                                                                            */
+  TFGPU_NATIVE_VALUE_TYPE = 14,     /* a value of another JSON type than the column's conversion takes (an array outside `any`, a bool in a number column …) */
+  TFGPU_NATIVE_TIME_ZONE = 15,      /* a time with a numeric zone offset (the ABI's time.Time is UTC)                                           */
+  TFGPU_NATIVE_TIME_FORM = 16,      /* a time only dateparse reads, more than nine fraction digits, a number in a time column                    */
+  TFGPU_NATIVE_BASE64 = 17,         /* a binary column whose string is not standard padded base64                                             */
+  TFGPU_NATIVE_ANY_STRING = 18,     /* a string in an `any` column that tryUnmarshalJSON decides                                               */
+  TFGPU_NATIVE_ANY_PG_TIMESTAMP = 19,/* a string in an `any` column of a pg:timestamp type                                                    */
+  TFGPU_NATIVE_MYSQL_BIT = 20,      /* a number in a mysql:bit column                                                                          */
+  TFGPU_NATIVE_STRING_NONSTRING = 21,/* a value that is no string in a string column                                                          */
+  TFGPU_NATIVE_MONGO_BSON = 22      /* a value in an `any` column of a mongo:bson type                                                         */
+} tfgpu_native_reason;
+/* One message left to the stock parser: item = the first offending item inside the message (-1: the message's own shape), column = its index in
+ * columnnames, len(columnnames) + k for keyvalues[k], -1 for anything else.                                                                       */
+typedef struct tfgpu_native_unparsed { int64_t msg; int32_t reason; int32_t item; int32_t column; } tfgpu_native_unparsed;
+typedef struct tfgpu_native_parsed tfgpu_native_parsed;
+/* Keys and headers are ignored; a nil value is a message without items.  TFGPU_ERR_UNSUPPORTED by name: values reaching 4 GiB (which also bounds the
+ * items below 2^31), a text column reaching 4 GiB, a group of more than 65 535 columns.  The handle belongs to the lane that made it.             */
+int tfgpu_native_parse(const tfgpu_message_batch *batch, tfgpu_native_parsed **out);
+/* the refusals and argument checks that need no byte of the batch (host code, no GPU)                                                             */
+int tfgpu_native_check_sizes(const tfgpu_message_batch *batch);
+/* nitems: every item of every message the cut found (fallen-back messages included, messages whose shape failed contribute none)                   */
+int tfgpu_native_parsed_info(const tfgpu_native_parsed *h, int64_t *nitems, int32_t *ngroups, int64_t *nfallback_msgs);
+/* *batch is a new handle over the group's buffers (free it with tfgpu_dbatch_free); meta, part and key_types ([*n_key_types]) live as long as `h`   */
+int tfgpu_native_parsed_group(const tfgpu_native_parsed *h, int32_t g, tfgpu_dbatch **batch, const tfgpu_row_meta **meta, const char **part,
+                              const char *const **key_types, int32_t *n_key_types);
+int tfgpu_native_parsed_group_schema(const tfgpu_native_parsed *h, int32_t g, const tfgpu_schema **schema, const char **table_schema_json);
+/* HOST arrays of nitems entries each, in item order: the item's message, its group (-1: in a fallen-back message) and its row in that group          */
+int tfgpu_native_parsed_items(const tfgpu_native_parsed *h, int64_t *msg, int32_t *group, int64_t *row);
+/* the fallen-back messages in message order; *n says how many there are even when cap is smaller                                                  */
+int tfgpu_native_parsed_fallback(const tfgpu_native_parsed *h, tfgpu_native_unparsed *list, int64_t cap, int64_t *n);
+void tfgpu_native_parsed_free(tfgpu_native_parsed *h);
+
 /* ---- profiling hooks (bench.py / rocprof cross-check) ------------------- */
 /* Per-kernel accumulated device time measured with HIP events on the library
  * stream.  Enable, run, then read back name/launches/total_ms.              */

@@ -182,6 +182,12 @@ PROTO_PKG = {"PackageTypeProtoseq": 0, "PackageTypeRepeated": 1, "PackageTypeSin
 PROTO_UNPARSED_DTYPE = np.dtype([("event", "<i8"), ("msg", "<i8"), ("start", "<u8"), ("len", "<u4"), ("idx", "<i4"), ("code", "<i4"), ("column", "<i4")])
 
 
+NATIVE_REASON = {0: "OK", 1: "SYNTAX", 2: "UTF8", 3: "DEPTH", 4: "KEY_FORM", 5: "DUP_MEMBER", 6: "HEADER_VALUE", 7: "KIND", 8: "LENGTHS", 9: "INSERT_KEYVALUES",
+                 10: "SCHEMA_DIFFERS", 11: "SCHEMA_COLUMN", 12: "INT_FORM", 13: "NUM_STRING", 14: "VALUE_TYPE", 15: "TIME_ZONE", 16: "TIME_FORM", 17: "BASE64",
+                 18: "ANY_STRING", 19: "ANY_PG_TIMESTAMP", 20: "MYSQL_BIT", 21: "STRING_NONSTRING", 22: "MONGO_BSON"}   # tfgpu_native_reason
+NATIVE_UNPARSED_DTYPE = np.dtype([("msg", "<i8"), ("reason", "<i4"), ("item", "<i4"), ("column", "<i4"), ("_pad", "<i4")])   # tfgpu_native_unparsed
+
+
 def message_batch(topic: str, partition: int, msgs) -> CMessageBatch:
     """parsers.MessageBatch → tfgpu_message_batch in host memory.  msgs: [(offset, write_time_ns, key | None, value | None, headers | None)], headers a
     dict (or a list of pairs, in the order given) of str / bytes → str / bytes.  None is Go's nil; b"" and {} are not."""

@@ -29,6 +29,7 @@
 #include "tf_plan.hpp"
 #include "tf_rows.hpp"
 #include "tf_devrow.hpp"
+#include "tf_intern.hpp"
 
 struct tfgpu_tablesplit {
   int64_t nrows = 0;
@@ -46,7 +47,6 @@ struct tfgpu_tablesplit {
 
 namespace tf {
 
-static constexpr uint32_t NOROW = 0xFFFFFFFFu;
 static inline unsigned tgrid(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + 255) / 256); }
 
 struct SplitParams {
@@ -60,23 +60,7 @@ struct SplitParams {
 };
 
 // ---- sinks ----------------------------------------------------------------------------------------------------------------
-struct NameHash {
-  uint64_t h1 = 0x452821E638D01377ull, h2 = 0xBE5466CF34E90C6Cull, acc = 0, len = 0;
-  uint32_t k = 0;
-  __device__ __forceinline__ void mix(uint64_t w) {
-    h1 = (h1 ^ w) * 0x9E3779B97F4A7C15ull; h1 ^= h1 >> 32;
-    h2 = (((h2 << 31) | (h2 >> 33)) ^ w) * 0xC2B2AE3D27D4EB4Full; h2 ^= h2 >> 29;
-  }
-  __device__ __forceinline__ void put(uint32_t c) {
-    acc |= (uint64_t)(c & 0xFFu) << (8 * k); len++;
-    if (++k == 8) { mix(acc); acc = 0; k = 0; }
-  }
-  __device__ __forceinline__ void finish() {
-    mix(acc); mix(len);
-    h1 ^= h1 >> 33; h1 *= 0xFF51AFD7ED558CCDull; h1 ^= h1 >> 33;
-    h2 ^= h2 >> 33; h2 *= 0xC4CEB9FE1A85EC53ull; h2 ^= h2 >> 33;
-  }
-};
+// (NameHash: tf_intern.hpp)
 struct NameCount { uint64_t n = 0; __device__ __forceinline__ void put(uint32_t) { n++; } };
 struct NameStore { uint8_t *dst; __device__ __forceinline__ void put(uint32_t c) { *dst++ = (uint8_t)c; } };
 struct NameWindow {  // the bytes [lo, lo + 64) of a rendered name
@@ -204,27 +188,8 @@ __global__ void __launch_bounds__(256) tsplit_intern_text(SplitParams p, uint32_
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) intern_row<true>(p, (int64_t)p.defer_list[i], owner, mask, slotof);
 }
 
-// ---- 3. first-appearance ids ----------------------------------------------------------------------------------------------
+// ---- 3. first-appearance ids: intern_first / intern_flag / intern_ids (tf_intern.hpp) over owner[] --------------------------------
 // (owner[slot] is some row of the slot's table: the minimum over all of them is the table's first row)
-__global__ void __launch_bounds__(256) tsplit_first(const uint32_t *__restrict__ slotof, int64_t n, uint32_t *owner) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  uint32_t *o = &owner[slotof[r]];
-  // (most rows come after the row that claimed their slot: with few tables the atomics of a million rows on a handful of addresses were the longest step)
-  if (__hip_atomic_load(o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)r) atomicMin(o, (uint32_t)r);
-}
-__global__ void __launch_bounds__(256) tsplit_flag(const uint32_t *__restrict__ slotof, const uint32_t *__restrict__ owner, int64_t n, uint32_t *__restrict__ flag) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n) flag[r] = owner[slotof[r]] == (uint32_t)r ? 1u : 0u;
-}
-__global__ void __launch_bounds__(256) tsplit_ids(const uint32_t *__restrict__ slotof, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ rank, int64_t n,
-                                                  uint32_t *__restrict__ tid, uint32_t *__restrict__ reps, uint32_t *__restrict__ idx) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  tid[r] = rank[owner[slotof[r]]];
-  if (rank[r + 1] != rank[r]) reps[rank[r]] = (uint32_t)r;
-  idx[r] = (uint32_t)r;
-}
 __global__ void __launch_bounds__(256) tsplit_kinds(const uint8_t *__restrict__ kind, int64_t n, uint32_t *flag) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r < n && kind[r] > TFGPU_K_DELETE) *flag = 1u;
@@ -246,11 +211,7 @@ __global__ void __launch_bounds__(256) tsplit_name_write(SplitParams p, const ui
   emit_name(p, (int64_t)reps[t], s);
 }
 
-// ---- 5. run heads of the sorted ids ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) tsplit_heads(const uint32_t *__restrict__ stid, int64_t n, uint32_t *__restrict__ start) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < n && (q == 0 || stid[q] != stid[q - 1])) start[stid[q]] = (uint32_t)q;
-}
+// ---- 5. run heads of the sorted ids: intern_heads (tf_intern.hpp) ------------------------------------------------------------
 
 // `cur`: the caller's own copy of the batch (the lane's mutex is held)
 static std::unique_ptr<tfgpu_tablesplit> split_batch(const tfgpu_plan &p, std::unique_ptr<tfgpu_dbatch> cur) {
@@ -327,10 +288,10 @@ static std::unique_ptr<tfgpu_tablesplit> split_batch(const tfgpu_plan &p, std::u
   }
   {
     KernelTimer t("tsplit_ids", n);
-    tsplit_first<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(slotof), n, ptr<uint32_t>(owner));
-    tsplit_flag<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(slotof), ptr<uint32_t>(owner), n, ptr<uint32_t>(rank));
+    intern_first<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(slotof), nullptr, n, ptr<uint32_t>(owner));
+    intern_flag<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(slotof), nullptr, ptr<uint32_t>(owner), n, ptr<uint32_t>(rank));
     exclusive_scan_u32(ptr<uint32_t>(rank), ptr<uint32_t>(rank), n, true);
-    tsplit_ids<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(slotof), ptr<uint32_t>(owner), ptr<uint32_t>(rank), n, ptr<uint32_t>(tid), ptr<uint32_t>(reps), ptr<uint32_t>(idx));
+    intern_ids<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(slotof), nullptr, ptr<uint32_t>(owner), ptr<uint32_t>(rank), n, NOROW, ptr<uint32_t>(tid), ptr<uint32_t>(reps), ptr<uint32_t>(idx));
   }
   const uint32_t *hT = d2h_u32(ptr<uint32_t>(rank) + n), *hk = d2h_u32(kflag->p);
   sync();
@@ -375,7 +336,7 @@ static std::unique_ptr<tfgpu_tablesplit> split_batch(const tfgpu_plan &p, std::u
       {
         KernelTimer ts("tsplit_sort", n);
         TF_HIP(rocprim::radix_sort_pairs(tmp->p, tmp_bytes, ptr<uint32_t>(tid), ptr<uint32_t>(stid), ptr<uint32_t>(idx), ptr<uint32_t>(sel), (size_t)n, 0u, bits, st));
-        tsplit_heads<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(stid), n, ptr<uint32_t>(start));
+        intern_heads<<<tgrid(n), 256, 0, st>>>(ptr<uint32_t>(stid), n, ptr<uint32_t>(start));
       }
       d2h(hstart.data(), start->p, hstart.size() * 4);
       sync();

@@ -40,6 +40,8 @@ EXPORTS = [
     "tfgpu_raw_to_table_parse", "tfgpu_raw_to_table_check_sizes", "tfgpu_rawtt_chunk_bytes", "tfgpu_rawtt_long_bytes",
     "tfgpu_proto_parser_create", "tfgpu_proto_parser_create_json", "tfgpu_proto_parser_free", "tfgpu_proto_parser_schema", "tfgpu_proto_parser_info",
     "tfgpu_proto_parser_parse",
+    "tfgpu_native_parse", "tfgpu_native_check_sizes", "tfgpu_native_parsed_info", "tfgpu_native_parsed_group", "tfgpu_native_parsed_group_schema",
+    "tfgpu_native_parsed_items", "tfgpu_native_parsed_fallback", "tfgpu_native_parsed_free",
 ]
 
 
@@ -187,6 +189,15 @@ def load():
     L.tfgpu_proto_parser_schema.argtypes = [P, C.POINTER(C.POINTER(abi.CSchema))]
     L.tfgpu_proto_parser_info.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
     L.tfgpu_proto_parser_parse.argtypes = [P, C.POINTER(abi.CMessageBatch), P, C.POINTER(P), P, C.c_int64, C.POINTER(C.c_int64), P]
+    L.tfgpu_native_parse.argtypes = [C.POINTER(abi.CMessageBatch), C.POINTER(P)]
+    L.tfgpu_native_check_sizes.argtypes = [C.POINTER(abi.CMessageBatch)]
+    L.tfgpu_native_parsed_info.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.tfgpu_native_parsed_group.argtypes = [P, C.c_int32, C.POINTER(P), C.POINTER(C.POINTER(abi.CRowMeta)), C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_int32)]
+    L.tfgpu_native_parsed_group_schema.argtypes = [P, C.c_int32, C.POINTER(C.POINTER(abi.CSchema)), C.POINTER(C.c_char_p)]
+    L.tfgpu_native_parsed_items.argtypes = [P, P, P, P]
+    L.tfgpu_native_parsed_fallback.argtypes = [P, P, C.c_int64, C.POINTER(C.c_int64)]
+    L.tfgpu_native_parsed_free.argtypes = [P]
+    L.tfgpu_native_parsed_free.restype = None
     _lib = L
     return L
 
@@ -1435,6 +1446,113 @@ class ProtoParser:
             self.free()
         except Exception:
             pass
+
+
+class NativeGroup:
+    """One group of a NativeParsed: an ordinary batch plus what a batch cannot say.  `meta` is a DEVICE-resident tfgpu_row_meta the parse result
+    owns: the group is valid while its NativeParsed lives."""
+
+    def __init__(self, batch: DeviceBatch, meta: abi.CRowMeta, part: str, key_types, schema: abi.Schema, table_schema_json):
+        self.batch, self.meta, self.part, self.key_types, self.schema, self.table_schema_json = batch, meta, part, key_types, schema, table_schema_json
+
+    def meta_host(self) -> dict:
+        """the meta arrays copied to the host: id, lsn, commit_time, counter, names_form as arrays, tx_id / query as lists of bytes"""
+        m, n = self.meta, int(self.meta.n)
+        assert m.mem == abi.MEM_DEVICE
+
+        def arr(p, dt, k):
+            out = np.zeros(max(k, 1), dt)
+            if k and p:
+                _d2h(p, out, k * out.itemsize)
+            return out[:k]
+
+        def var(po, pd):
+            off = arr(po, np.uint32, n + 1)
+            dat = arr(pd, np.uint8, int(off[-1]) if n else 0)
+            return [bytes(dat[int(off[i]):int(off[i + 1])]) for i in range(n)]
+        return {"id": arr(m.id, np.uint32, n), "lsn": arr(m.lsn, np.uint64, n), "commit_time": arr(m.commit_time, np.uint64, n), "counter": arr(m.counter, np.int64, n),
+                "names_form": arr(m.names_form, np.uint8, n), "tx_id": var(m.tx_id_offsets, m.tx_id_data), "query": var(m.query_offsets, m.query_data)}
+
+
+def _d2h(dev_ptr: int, out: np.ndarray, nbytes: int):
+    """device memory of the library's lane -> a host array, through a batch view's download path: wraps the bytes as a one-column uint8 DEVICE batch"""
+    if not nbytes:
+        return
+    col = abi.CColumn()
+    col.name, col.dtype, col.repr, col.values = b"b", abi.DTYPE_ID["uint8"], abi.R_UINT8, dev_ptr
+    cb = abi.CBatch()
+    cb.nrows, cb.ncols, cb.cols, cb.mem = nbytes, 1, C.pointer(col), abi.MEM_DEVICE
+    h = C.c_void_p()
+    _check(load().tfgpu_batch_upload(C.byref(cb), C.byref(h)))
+    got = DeviceBatch(h).download().cols[0].values
+    out.view(np.uint8).reshape(-1)[:nbytes] = got[:nbytes]
+
+
+class NativeParsed:
+    """tfgpu_native_parse's result: the groups (ordinary batches + row meta, PartID, OldKeys.KeyTypes, the full TableSchema), the item map and the
+    messages left to the stock parser."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def info(self):
+        """(items, groups, fallen-back messages)"""
+        ni, ng, nf = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        _check(load().tfgpu_native_parsed_info(self._h, C.byref(ni), C.byref(ng), C.byref(nf)))
+        return int(ni.value), int(ng.value), int(nf.value)
+
+    def group(self, g: int) -> NativeGroup:
+        b, meta, part, kt, nkt = C.c_void_p(), C.POINTER(abi.CRowMeta)(), C.c_char_p(), C.POINTER(C.c_char_p)(), C.c_int32(0)
+        _check(load().tfgpu_native_parsed_group(self._h, g, C.byref(b), C.byref(meta), C.byref(part), C.byref(kt), C.byref(nkt)))
+        sch, tsj = C.POINTER(abi.CSchema)(), C.c_char_p()
+        _check(load().tfgpu_native_parsed_group_schema(self._h, g, C.byref(sch), C.byref(tsj)))
+        grp = NativeGroup(DeviceBatch(b), meta.contents, (part.value or b"").decode("utf-8", "surrogateescape"), [kt[i] for i in range(nkt.value)],
+                          abi.Schema.from_c(sch.contents), tsj.value)
+        grp._owner = self
+        return grp
+
+    def groups(self):
+        return [self.group(g) for g in range(self.info()[1])]
+
+    def items(self):
+        """(message, group or -1, row or -1) per item, in item order"""
+        n = self.info()[0]
+        msg, grp, row = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64)
+        _check(load().tfgpu_native_parsed_items(self._h, msg.ctypes.data, grp.ctypes.data, row.ctypes.data))
+        return msg[:n], grp[:n], row[:n]
+
+    def fallback(self):
+        """[(message, reason name, item, column)] in message order"""
+        n = self.info()[2]
+        buf = np.zeros(max(n, 1), abi.NATIVE_UNPARSED_DTYPE)
+        k = C.c_int64(0)
+        _check(load().tfgpu_native_parsed_fallback(self._h, buf.ctypes.data, n, C.byref(k)))
+        assert int(k.value) == n
+        return [(int(r["msg"]), abi.NATIVE_REASON[int(r["reason"])], int(r["item"]), int(r["column"])) for r in buf[:n]]
+
+    def free(self):
+        if self._h:
+            load().tfgpu_native_parsed_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def native_parse(batch: abi.CMessageBatch) -> NativeParsed:
+    """The native parser (pkg/parsers/registry/native): messages written by the NATIVE queue format back to typed batches"""
+    init()
+    h = C.c_void_p()
+    _check(load().tfgpu_native_parse(C.byref(batch), C.byref(h)))
+    return NativeParsed(h)
+
+
+def native_check_sizes(batch):
+    """the argument checks and size refusals of native_parse alone (host code); `batch` may be None"""
+    _check(load().tfgpu_native_check_sizes(C.byref(batch) if batch is not None else None))
 
 
 def raw_to_table_check_sizes(batch: abi.CMessageBatch):
